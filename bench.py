@@ -1,7 +1,20 @@
 """GLL fwd+bwd throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config ns|fullysup|stress|plumbing]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...        (one process per GPU)
+
+A plain run does only what the headline needs: set-up, W warm-up steps (and the short untimed
+probe that picks the autograd engine's threading mode, see --autograd-thread), the K timed
+steps, the output dump if asked for, and the JSON line.  `--full` adds everything else the
+line can carry, each in a pass of its own after the timed steps: per-kernel event timings and
+the rooflines, the C-ABI rate, the other engine threading mode, the adversarial callers'
+auto-eps call, the batched entry point and the CPU baseline (--no-profile, --batch 0 and
+--cpu-seconds 0 switch parts of it off); without it those fields are null.
+`--dump-outputs DIR` writes what the last timed step returned to its caller -- the predictions
+U (float64) and the feature gradient grad_X (float32) -- as DIR/U.npy and DIR/grad_X.npy
+(ranks past 0 add a `_rank<r>` suffix).  The inputs are seeded, so two builds can be compared
+array for array.  Past 63 MiB in all, a fixed seeded sample of the flattened array is written.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself: it runs
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` as a child
@@ -61,12 +74,20 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="ns", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (kernel events and "
+                         "rooflines, C ABI, other autograd mode, auto-eps call, batched entry, "
+                         "CPU baseline), each in a pass of its own after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (U, grad_X) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="budget of the CPU-baseline sample (rank 0, N=1 only); 0 disables")
-    ap.add_argument("--no-profile", action="store_true", help="skip kernel event timing")
+                    help="with --full: budget of the CPU-baseline sample (rank 0, N=1 only); "
+                         "0 disables")
+    ap.add_argument("--no-profile", action="store_true",
+                    help="with --full: skip kernel event timing")
     ap.add_argument("--batch", type=int, default=64,
-                    help="graphs per launch of the batched entry point measured beside the "
-                         "headline (SURVEY.md §8f-2); 0 disables")
+                    help="with --full: graphs per launch of the batched entry point measured "
+                         "beside the headline (SURVEY.md §8f-2); 0 disables")
     ap.add_argument("--share-gpu", action="store_true",
                     help="diagnostic: every rank on cuda:0 over gloo (RCCL refuses two ranks on "
                          "one GPU), to run the real multi-rank GPU leg on a one-GPU box; the "
@@ -406,6 +427,27 @@ def c_abi_measure(X, Y, tau, eps, k, gbar, steps, warmup):
                     "no torch autograd engine on the host path"}
 
 
+DUMP_CAP_BYTES = 63 * 2 ** 20   # of array data over all files of one dump
+
+
+def dump_outputs(path, arrays, suffix=""):
+    """Write each tensor of `arrays` as path/<name><suffix>.npy, float32 or float64.  When the
+    arrays together pass DUMP_CAP_BYTES, an array larger than its equal share of the cap is
+    replaced by a fixed seeded sample of its flattened entries (in index order)."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        v = np.ascontiguousarray(t.detach().cpu().numpy())
+        host[name] = v if v.dtype in (np.float32, np.float64) else v.astype(np.float32)
+    total = sum(v.nbytes for v in host.values())
+    share = DUMP_CAP_BYTES // max(len(host), 1)
+    for name, v in host.items():
+        if total > DUMP_CAP_BYTES and v.nbytes > share:
+            idx = np.random.default_rng(0).choice(v.size, share // v.itemsize, replace=False)
+            v = v.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), v)
+
+
 def _cpu_model() -> str:
     try:
         with open("/proc/cpuinfo") as f:
@@ -496,12 +538,15 @@ def dry_run(a, world, rank):
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
+    U = base_u
     for s in range(a.steps):
-        step(a.warmup + s)
+        U = step(a.warmup + s)
     gatherer.wait()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"U": U}, f"_rank{rank}" if rank else "")
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -578,7 +623,8 @@ def main():
     names = [_lib.kernel_name(q) for q in range(_lib.K_COUNT)]
     per_kernel = {}
     dominant = None
-    if not a.no_profile:
+    profile = a.full and not a.no_profile
+    if profile:
         for q in range(_lib.K_COUNT):
             _lib.prof_enable(q, 1)
         # as many bracketed steps as the timed region will sample, so that every event pair it
@@ -667,6 +713,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    # what the last timed step handed its caller (the passes above discard theirs)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"U": U, "grad_X": gx}, f"_rank{rank}" if rank else "")
 
     # which GPU each rank ran on, as the process group sees it (one tiny all_gather, outside the
     # timed region): a scaling line carries its own proof of N distinct devices and N ranks
@@ -764,12 +814,12 @@ def main():
                     v["pmc_traffic_over_algorithmic"] = round(pt / w_, 3) if b_ == "hbm" else None
 
     c_abi = None
-    if not a.no_profile:
+    if profile:
         c_abi = c_abi_measure(X, Y, tau, eps, k, gbar, a.steps, a.warmup)
 
     # the same step with the autograd engine's other threading mode (labelled, not `value`)
     other = None
-    if world == 1 and not a.no_profile:
+    if world == 1 and profile:
         with torch.autograd.set_multithreading_enabled(a.autograd_thread != "device"):
             for _ in range(a.warmup):
                 step()
@@ -788,7 +838,7 @@ def main():
     # adversarial.py:534): lap(features, one_hot(labels)[:k]) -- int64 labels, tau = 0, eps =
     # 'auto' -- on the same graph, through apply + autograd.grad (labelled extra, not `value`)
     auto_extra = None
-    if a.config == "ns" and not a.no_profile and world == 1:
+    if a.config == "ns" and profile and world == 1:
         Yi = Y.to(torch.int64)
         per_k = {}
 
@@ -830,7 +880,7 @@ def main():
         batched = batched_measure(c, eps, tau, k, a.batch, gstats, dev, rank)
 
     cpu = None
-    if rank == 0 and world == 1 and a.cpu_seconds > 0:
+    if a.full and rank == 0 and world == 1 and a.cpu_seconds > 0:
         cpu = cpu_baseline(c, eps, tau, a.cpu_seconds, a.config)
 
     if rank == 0:
@@ -847,6 +897,7 @@ def main():
             "steps": a.steps,
             "warmup": a.warmup,
             "ms_per_step": round(1e3 * elapsed / a.steps, 4),
+            "full": a.full,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
