@@ -18,7 +18,12 @@ Deliberate differences from the reference (all documented in DESIGN.md):
   * outputs are placed on X.device (the reference uses the *current* device, GLL.py:15-18);
   * an optional 5th positional argument `k` replaces the hard-coded k=25 (GLL.py:27);
   * X may carry a leading batch dimension (B x n x d, labels B x base x C or shared):
-    B independent graphs in one launch per kernel, U is B x m x C.
+    B independent graphs in one launch per kernel (SURVEY.md §8f-2), U is B x m x C;
+  * label_matrix (floating point), tau and a fixed epsilon are differentiable as well as X
+    (the reference returns None for them, GLL.py:177): tau / epsilon may be one-element
+    tensors, whose value is read once in the forward (a host sync when on the GPU), and their
+    gradients come from one extra pass over the graph (gll_param_grad_batched, DESIGN.md
+    §3.6); epsilon='auto' has no epsilon input and so no epsilon gradient.
 """
 from __future__ import annotations
 
@@ -134,12 +139,26 @@ def _typed(t: torch.Tensor, dev):
     return t.contiguous(), code
 
 
+def _scalar_tensor(v, what):
+    """True when tau / epsilon is given as a tensor: it must hold one floating-point value."""
+    if not torch.is_tensor(v):
+        return False
+    if v.numel() != 1 or not v.is_floating_point():
+        raise TypeError(f"{what} as a tensor must hold one floating-point value")
+    return True
+
+
 def _eps_value(epsilon) -> float:
     if isinstance(epsilon, str):
         if epsilon != "auto":
             raise ValueError(f"epsilon must be a number or 'auto', got {epsilon!r}")
         return 0.0
-    e = float(epsilon)
+    if _scalar_tensor(epsilon, "epsilon"):
+        e = epsilon.item()
+        if epsilon.requires_grad and not e > 0.0:
+            raise ValueError("epsilon as a tensor that requires grad must be > 0")
+    else:
+        e = float(epsilon)
     if not e > 0.0:
         # GLL.py:240-241 warns for any eps < 1e-10.  The reference uses eps only as the product
         # eps[rows] * eps[cols] (GLL.py:233-234), so a negative eps builds the graph of |eps|;
@@ -152,7 +171,9 @@ def _eps_value(epsilon) -> float:
 def make_problem(n, d, base, C, k=DEFAULT_K, tau=0.0, epsilon="auto",
                  rtol=DEFAULT_RTOL, max_iter=DEFAULT_MAX_ITER, flags=0) -> _lib.Problem:
     return _lib.Problem(n=int(n), d=int(d), base=int(base), C=int(C), K=int(min(k, n)),
-                        max_iter=int(max_iter), tau=float(tau), eps=_eps_value(epsilon),
+                        max_iter=int(max_iter),
+                        tau=tau.item() if _scalar_tensor(tau, "tau") else float(tau),
+                        eps=_eps_value(epsilon),
                         rtol=float(rtol), flags=int(flags))
 
 
@@ -209,6 +230,10 @@ class LaplaceLearningSparseHard(torch.autograd.Function):
             _ext_mod.note_call(dev.index)
         ctx.save_for_backward(X)
         ctx.prob, ctx.ws, ctx.dev, ctx.B = prob, ws, dev, B
+        # what the label_matrix / tau / epsilon gradients take after: (dtype, device, shape)
+        ctx.like = [(t.dtype, t.device, t.shape) if torch.is_tensor(t) else None
+                    for t in (label_matrix, tau, epsilon)]
+        ctx.Y_shared = X.dim() == 3 and label_matrix.dim() == 2
         return U if X.is_cuda else U.cpu()
 
     @staticmethod
@@ -225,9 +250,45 @@ class LaplaceLearningSparseHard(torch.autograd.Function):
                                                        ctx.ws.data_ptr(), g.data_ptr(), gdt,
                                                        gradX.data_ptr(), _stream(dev)),
                        "gll_backward")
-        if gradX.device != X.device or gradX.dtype != X.dtype:
+            need = ctx.needs_input_grad
+            what = ((_lib.PG_Y if need[1] and ctx.like[0][0].is_floating_point else 0)
+                    | (_lib.PG_TAU if need[2] else 0)
+                    | (_lib.PG_EPS if need[3] and prob.eps > 0.0 else 0))
+            gY = gtau = geps = None
+            if what:   # one more pass over the graph the backward just completed
+                B = ctx.B
+                f64 = dict(dtype=torch.float64, device=dev)
+                bufY = torch.empty((B, prob.base, prob.C), dtype=torch.float32, device=dev) \
+                    if what & _lib.PG_Y else None
+                btau = torch.empty(B, **f64) if what & _lib.PG_TAU else None
+                beps = torch.empty(B, **f64) if what & _lib.PG_EPS else None
+                scratch = torch.empty(_lib.lib().gll_param_grad_scratch_bytes(ct.byref(prob), B),
+                                      dtype=torch.uint8, device=dev) \
+                    if what & (_lib.PG_TAU | _lib.PG_EPS) else None
+
+                def ptr(t):
+                    return None if t is None else t.data_ptr()
+
+                _lib.check(_lib.lib().gll_param_grad_batched(ct.byref(prob), B, ctx.ws.data_ptr(),
+                                                             what, ptr(bufY), ptr(btau), ptr(beps),
+                                                             ptr(scratch), _stream(dev)),
+                           "gll_param_grad")
+
+                def like(v, meta):   # the input's dtype, device and shape
+                    return v.to(device=meta[1], dtype=meta[0]).reshape(meta[2])
+
+                # batched input: shared labels and the scalars sum over graphs (float64)
+                if bufY is not None:
+                    gY = like(bufY.double().sum(0) if ctx.Y_shared else bufY, ctx.like[0])
+                if btau is not None:
+                    gtau = like(btau.sum() if B > 1 else btau, ctx.like[1])
+                if beps is not None:
+                    geps = like(beps.sum() if B > 1 else beps, ctx.like[2])
+        if not ctx.needs_input_grad[0]:
+            gradX = None
+        elif gradX.device != X.device or gradX.dtype != X.dtype:
             gradX = gradX.to(device=X.device, dtype=X.dtype)
-        return gradX, None, None, None, None
+        return gradX, gY, gtau, geps, None
 
 
 # ----------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 // api.hip -- the extern "C" boundary declared in include/gll.h.
 //
-// Orchestrates the kernels of knn.hip, rows.hip, solve.hip / gridcg.hip and grad.hip on the caller's
+// Orchestrates the kernels of knn.hip, rows.hip, solve.hip / gridcg.hip, grad.hip and param_grad.hip on the caller's
 // stream.  No allocation, no host synchronisation: the caller owns the workspace (the
 // Python mirror takes it from torch's caching allocator) and keeps it alive from
 // gll_forward to gll_backward, as the reference keeps its graph on ctx (GLL.py:69-70).
@@ -152,7 +152,8 @@ size_t static_lds_bytes(const void* fn) {
 
 static const char* kKernelNames[GLL_K_COUNT] = {
     "gram_d2_kernel", "knn_select_kernel", "row_build_kernel",
-    "cg_kernel",      "edge_coef_kernel",  "grad_spmm_kernel", "cg_grad_fused_kernel"};
+    "cg_kernel",      "edge_coef_kernel",  "grad_spmm_kernel", "cg_grad_fused_kernel",
+    "param_grad_kernel"};
 
 static bool vec_ok(const float* X, int d) {
     return (d % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
@@ -317,6 +318,30 @@ int gll_forward_batched(const gll_problem* p, int B, const float* X, const void*
 int gll_backward_batched(const gll_problem* p, int B, const float* X, void* ws, const void* gbar,
                          int g_dtype, float* gradX, void* stream) {
     return backward_impl(p, B, X, ws, gbar, g_dtype, gradX, stream);
+}
+
+size_t gll_param_grad_scratch_bytes(const gll_problem* p, int B) {
+    if (check(p) != GLL_OK || B < 1 || B > 65535) return 0;
+    return param_grad_scratch_bytes(p->n, B);
+}
+
+int gll_param_grad_batched(const gll_problem* p, int B, void* ws, int what, float* gradY,
+                           double* grad_tau, double* grad_eps, void* scratch, void* stream) {
+    int rc = check(p);
+    if (rc != GLL_OK) return rc;
+    if (B < 1 || B > 65535) return GLL_ERR_INVALID_ARG;
+    if (what & ~(GLL_PG_Y | GLL_PG_TAU | GLL_PG_EPS)) return GLL_ERR_INVALID_ARG;
+    if ((what & GLL_PG_EPS) && !(p->eps > 0.f)) return GLL_ERR_INVALID_ARG;   // 'auto': no eps input
+    if (!ws) return GLL_ERR_INVALID_ARG;
+    if ((what & GLL_PG_Y) && p->base > 0 && !gradY) return GLL_ERR_INVALID_ARG;
+    if ((what & GLL_PG_TAU) && !grad_tau) return GLL_ERR_INVALID_ARG;
+    if ((what & GLL_PG_EPS) && !grad_eps) return GLL_ERR_INVALID_ARG;
+    if ((what & (GLL_PG_TAU | GLL_PG_EPS)) && !scratch) return GLL_ERR_INVALID_ARG;
+    if ((what & GLL_PG_Y) && p->base == 0) what &= ~GLL_PG_Y;   // no labeled rows: nothing to write
+    if (what == 0) return GLL_OK;
+    Layout L(*p);
+    return hip_status(launch_param_grad(L, B, ws, p->eps, what, gradY, grad_tau, grad_eps, scratch,
+                                        static_cast<hipStream_t>(stream)));
 }
 
 int gll_workspace_view(const gll_problem* p, void* ws, gll_view* out) {

@@ -645,5 +645,12 @@ hipError_t launch_cg_grad_fused(const Layout& L, void* ws, const void* gbar, int
                                 const float* X, float eps_fixed, float* gradX, float rtol,
                                 int max_iter, int32_t* st_nonconv, int32_t* st_iters,
                                 int32_t* st_failed, bool vec, hipStream_t s);
+// Gradients of label_matrix / tau / fixed eps from the workspace a backward left behind
+// (param_grad.hip): `what` GLL_PG_* bits, `scratch` param_grad_scratch_bytes(n, B) bytes of
+// float64 row partials (only read and written when a scalar is selected).
+size_t param_grad_scratch_bytes(int n, int B);
+hipError_t launch_param_grad(const Layout& L, int B, void* ws, float eps_fixed, int what,
+                             float* gradY, double* grad_tau, double* grad_eps, void* scratch,
+                             hipStream_t s);
 
 }  // namespace gll

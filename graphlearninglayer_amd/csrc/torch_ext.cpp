@@ -6,8 +6,11 @@
 //   * `apply(X, label_matrix, tau=0, epsilon='auto', k=25)` is a METH_FASTCALL CPython function
 //     (no pybind dispatch, no Python frame): argument checks with the reference's error
 //     behaviour, tensor marshalling, the workspace from torch's caching allocator, gll_forward on
-//     the current HIP stream, and -- when X requires grad -- one autograd Node with its saved
-//     state in plain members (no IValue map, no torch::autograd::Function bookkeeping);
+//     the current HIP stream, and -- when X, label_matrix or a tensor tau / epsilon requires
+//     grad -- one autograd Node with its saved state in plain members (no IValue map, no
+//     torch::autograd::Function bookkeeping).  The node's backward is gll_backward_batched, plus
+//     one gll_param_grad_batched call when a gradient of label_matrix, tau or epsilon is wanted
+//     (the reference returns None for them, GLL.py:177);
 //   * the device status words (tiny eps, CG non-convergence, grid-barrier failure) accumulate in
 //     a sticky per-device sink that is copied to pinned memory every kFlushEvery calls and turned
 //     into the reference's warnings (GLL.py:240-241, 273-274) at a later call, with no host sync.
@@ -234,12 +237,32 @@ double g_grad_diag = -1.0;
 // ------------------------------------------------------------------------------------------
 // The autograd node: gll_backward over the saved workspace (GLL.py:76-177)
 // ------------------------------------------------------------------------------------------
+// Metadata of an input whose gradient takes that input's dtype, device and shape.
+struct GradLike {
+    int slot = -1;   // index among the node's inputs (next edges); < 0: not a tensor input
+    std::vector<int64_t> sizes;
+    at::ScalarType dtype = at::kFloat;
+    c10::Device device = c10::Device(c10::kCPU);
+
+    void set(int s, const at::Tensor& t) {
+        slot = s;
+        sizes = t.sizes().vec();
+        dtype = t.scalar_type();
+        device = t.device();
+    }
+    at::Tensor like(const at::Tensor& v) const { return v.to(device, dtype).reshape(sizes); }
+};
+
 struct LaplaceBackward : public torch::autograd::Node {
     torch::autograd::SavedVariable X_;
     at::Tensor ws_;
     gll_problem p_{};
     int64_t B_ = 1;
     double diag_ = -1.0;
+    // inputs in edge order: X, label_matrix, then tau and epsilon where they are tensors
+    int n_inputs_ = 1;
+    GradLike Y_, tau_, eps_;
+    bool Y_shared_ = false;   // 2-D label_matrix with batched X: the gradient sums over graphs
 
     std::string name() const override { return "LaplaceLearningSparseHardBackward"; }
 
@@ -252,7 +275,8 @@ struct LaplaceBackward : public torch::autograd::Node {
     variable_list apply(variable_list&& grads) override {
         std::lock_guard<std::mutex> lk(mutex_);
         const at::Tensor X = X_.unpack(shared_from_this());   // raises on a second backward
-        if (!grads[0].defined()) return {at::Tensor()};
+        variable_list out(n_inputs_);
+        if (!grads[0].defined()) return out;
         const c10::Device dev = ws_.device();
         c10::DeviceGuard guard(dev);
         at::Tensor X32 = features(X, dev);
@@ -266,9 +290,44 @@ struct LaplaceBackward : public torch::autograd::Node {
                                       current_stream(dev.index())),
                  "gll_backward");
         if (diag_ >= 0.0) report_gradient(g, gradX);
-        if (gradX.device() != X.device() || gradX.scalar_type() != X.scalar_type())
-            gradX = gradX.to(X.device(), X.scalar_type());
-        return {gradX};
+        int what = 0;
+        if (Y_.slot >= 0 && at::isFloatingType(Y_.dtype) && task_should_compute_output(Y_.slot))
+            what |= GLL_PG_Y;
+        if (tau_.slot >= 0 && task_should_compute_output(tau_.slot)) what |= GLL_PG_TAU;
+        if (eps_.slot >= 0 && p_.eps > 0.f && task_should_compute_output(eps_.slot))
+            what |= GLL_PG_EPS;
+        if (what) param_grads(what, X32, out);
+        if (task_should_compute_output(0)) {
+            if (gradX.device() != X.device() || gradX.scalar_type() != X.scalar_type())
+                gradX = gradX.to(X.device(), X.scalar_type());
+            out[0] = gradX;
+        }
+        return out;
+    }
+
+    // label_matrix / tau / epsilon gradients: one gll_param_grad_batched over the workspace the
+    // backward just completed.  Batched input: shared labels and the scalars sum over graphs
+    // (float64).
+    void param_grads(int what, const at::Tensor& X32, variable_list& out) {
+        const c10::Device dev = ws_.device();
+        const auto f64 = X32.options().dtype(at::kDouble);
+        at::Tensor gY, gtau, geps, scratch;
+        if (what & GLL_PG_Y) gY = at::empty({B_, int64_t(p_.base), int64_t(p_.C)}, X32.options());
+        if (what & GLL_PG_TAU) gtau = at::empty({B_}, f64);
+        if (what & GLL_PG_EPS) geps = at::empty({B_}, f64);
+        if (what & (GLL_PG_TAU | GLL_PG_EPS))
+            scratch = at::empty({int64_t(gll_param_grad_scratch_bytes(&p_, int(B_)))},
+                                X32.options().dtype(at::kByte));
+        check_rc(gll_param_grad_batched(&p_, int(B_), ws_.data_ptr(), what,
+                                        gY.defined() ? gY.data_ptr<float>() : nullptr,
+                                        gtau.defined() ? gtau.data_ptr<double>() : nullptr,
+                                        geps.defined() ? geps.data_ptr<double>() : nullptr,
+                                        scratch.defined() ? scratch.data_ptr() : nullptr,
+                                        current_stream(dev.index())),
+                 "gll_param_grad");
+        if (what & GLL_PG_Y) out[Y_.slot] = Y_.like(Y_shared_ ? gY.to(at::kDouble).sum(0) : gY);
+        if (what & GLL_PG_TAU) out[tau_.slot] = tau_.like(B_ > 1 ? gtau.sum() : gtau);
+        if (what & GLL_PG_EPS) out[eps_.slot] = eps_.like(B_ > 1 ? geps.sum() : geps);
     }
 
     // train_and_adversarial.py:177-183 (synchronises: diagnostic mode only)
@@ -302,17 +361,34 @@ double parse_float(PyObject* o, const char* what) {
     return v;
 }
 
+// tau / epsilon given as a tensor (0-dim or one element, any float dtype, any device): its value
+// is read once here -- a host synchronisation when it lives on the GPU -- and it becomes an
+// input of the autograd node.
+bool scalar_tensor_arg(PyObject* o, const char* what, at::Tensor& t, double& v) {
+    if (!THPVariable_Check(o)) return false;
+    t = THPVariable_Unpack(o);
+    if (t.numel() != 1 || !at::isFloatingType(t.scalar_type()))
+        raise_py(PyExc_TypeError, std::string(what) + " as a tensor must hold one floating-point value");
+    v = t.item<double>();
+    return true;
+}
+
 // epsilon: a number > 0 (fixed, GLL.py:226) or 'auto' (GLL.py:200-205) -> <= 0 for the ABI
-double parse_eps(PyObject* o) {
-    if (PyUnicode_Check(o)) {
+double parse_eps(PyObject* o, at::Tensor& t) {
+    double e;
+    if (scalar_tensor_arg(o, "epsilon", t, e)) {
+        if (t.requires_grad() && !(e > 0.0))
+            raise_py(PyExc_ValueError, "epsilon as a tensor that requires grad must be > 0");
+    } else if (PyUnicode_Check(o)) {
         if (PyUnicode_CompareWithASCIIString(o, "auto") != 0) {
             const char* s = PyUnicode_AsUTF8(o);
             raise_py(PyExc_ValueError,
                      std::string("epsilon must be a number or 'auto', got '") + (s ? s : "?") + "'");
         }
         return 0.0;
+    } else {
+        e = parse_float(o, "epsilon");
     }
-    const double e = parse_float(o, "epsilon");
     if (!(e > 0.0)) {
         // GLL.py:240-241 warns for any eps < 1e-10.  The reference uses eps only as the product
         // eps[rows] * eps[cols] (GLL.py:233-234), so a negative eps builds the graph of |eps|;
@@ -349,8 +425,10 @@ PyObject* apply_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames)
     if (!a[0] || !a[1]) raise_py(PyExc_TypeError, "apply() needs X and label_matrix");
     const at::Tensor& X = tensor_arg(a[0], "X");
     const at::Tensor& Y = tensor_arg(a[1], "label_matrix");
-    const double tau = a[2] ? parse_float(a[2], "tau") : 0.0;
-    const double eps = a[3] ? parse_eps(a[3]) : 0.0;
+    at::Tensor tau_t, eps_t;   // defined where tau / epsilon came as tensors
+    double tau = 0.0;
+    if (a[2] && !scalar_tensor_arg(a[2], "tau", tau_t, tau)) tau = parse_float(a[2], "tau");
+    const double eps = a[3] ? parse_eps(a[3], eps_t) : 0.0;
     int64_t k = kDefaultK;
     if (a[4]) {
         k = PyLong_AsLongLong(a[4]);
@@ -406,10 +484,18 @@ PyObject* apply_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames)
                                  ws.data_ptr(), U.data_ptr<double>(), s),
              "gll_forward");
     after_call(st, devi, s);
-    if (torch::autograd::compute_requires_grad(X)) {
+    std::vector<at::Tensor> inputs{X, Y};
+    if (tau_t.defined()) inputs.push_back(tau_t);
+    if (eps_t.defined()) inputs.push_back(eps_t);
+    if (torch::autograd::compute_requires_grad(inputs)) {
         auto node = std::shared_ptr<LaplaceBackward>(new LaplaceBackward(),
                                                      torch::autograd::deleteNode);
-        node->set_next_edges(torch::autograd::collect_next_edges(X));
+        node->set_next_edges(torch::autograd::collect_next_edges(inputs));
+        node->n_inputs_ = int(inputs.size());
+        node->Y_.set(1, Y);
+        node->Y_shared_ = batched && Y.dim() == 2;
+        if (tau_t.defined()) node->tau_.set(2, tau_t);
+        if (eps_t.defined()) node->eps_.set(tau_t.defined() ? 3 : 2, eps_t);
         node->X_ = torch::autograd::SavedVariable(X, false);
         node->ws_ = std::move(ws);
         node->p_ = p;
@@ -438,7 +524,9 @@ PyMethodDef kApplyDef = {
     "apply", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(apply_py)),
     METH_FASTCALL | METH_KEYWORDS,
     "U = LaplaceLearningSparseHard.apply(X, label_matrix, tau=0, epsilon='auto', k=25)\n"
-    "(GLL.py:14; k: neighbours incl. self, the reference hard-codes 25)"};
+    "(GLL.py:14; k: neighbours incl. self, the reference hard-codes 25).  X, a floating-point\n"
+    "label_matrix and tau / a fixed epsilon given as one-element tensors are differentiable\n"
+    "(a tensor's value is read once in the forward: a host sync when it lives on the GPU)"};
 
 // ------------------------------------------------------------------------------------------
 // status API for the Python layer

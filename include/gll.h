@@ -150,6 +150,28 @@ int gll_forward_batched(const gll_problem* p, int B, const float* X, const void*
 int gll_backward_batched(const gll_problem* p, int B, const float* X, void* workspace,
                          const void* gbar, int g_dtype, float* gradX, void* stream);
 
+/* Gradients of the inputs the reference leaves without one (GLL.py:177 returns None for
+ * label_matrix, tau and epsilon).  For the frozen kNN graph, with w = [0; Luu^-1 gbar] (the
+ * adjoint gll_backward leaves in the workspace), P = [Y; U], W_ij = exp(-4 d_ij^2 / eps^2) and
+ * G_ij = sum_c (w_ic - w_jc)(P_jc - P_ic):
+ *   grad_Y[j, c] = sum_{i in N(j)} W_ji w_ic                        rows j < base
+ *   grad_tau     = - sum_{i >= base, c} w_ic U_ic
+ *   grad_eps     = 1/2 sum_{directed edges (i, j)} G_ij W_ij 8 d_ij^2 / eps^3      fixed eps only
+ * (grad_Y and grad_tau hold for fixed and for 'auto' eps.)  Call after gll_backward(_batched)
+ * on the same workspace(s) and problem.  `what`: GLL_PG_* bits; gradY: B x base x C fp32;
+ * grad_tau, grad_eps: B float64 (one per graph); an output not selected in `what` may be NULL.
+ * `scratch`: gll_param_grad_scratch_bytes(p, B) bytes of device memory (float64 row partials;
+ * may be NULL when neither scalar is selected).  One pass over the graph rows, then a fixed-order
+ * float64 sum per graph: no atomics, bitwise reproducible, and graph g of a batch equals the
+ * single call.  base == 0 with GLL_PG_Y writes nothing. */
+#define GLL_PG_Y   1
+#define GLL_PG_TAU 2
+#define GLL_PG_EPS 4   /* GLL_ERR_INVALID_ARG when p->eps <= 0 ('auto') */
+size_t gll_param_grad_scratch_bytes(const gll_problem* p, int B);
+int gll_param_grad_batched(const gll_problem* p, int B, void* workspace, int what,
+                           float* gradY, double* grad_tau, double* grad_eps,
+                           void* scratch, void* stream);
+
 /* Graph only (the device half of knn_sym_dist, GLL.py:180-244): kNN search, symmetric
  * CSR, eps, weights and degrees into the workspace; no solve.  Requires p->base == 0
  * (no labeled block; size the workspace for that problem).  Read the arrays with
@@ -201,7 +223,9 @@ int gll_cg_csr(int m, int C, const int32_t* row_ptr, const int32_t* col, const f
 #define GLL_K_GRAD 5      /* grad_spmm_kernel: feature gradient */
 #define GLL_K_BWD 6       /* cg_grad_fused_kernel: adjoint CG + feature gradient in one launch
                            * (single small graphs, fixed eps) */
-#define GLL_K_COUNT 7
+#define GLL_K_PARAM 7     /* param_grad_kernel (+ param_reduce_kernel): label_matrix / tau / eps
+                           * gradients (gll_param_grad_batched) */
+#define GLL_K_COUNT 8
 int gll_prof_enable(int kid, int period);
 int gll_prof_read(int kid, double* ms_total, int* count);
 const char* gll_kernel_name(int kid);
