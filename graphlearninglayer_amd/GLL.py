@@ -19,6 +19,9 @@ Deliberate differences from the reference (all documented in DESIGN.md):
   * an optional 5th positional argument `k` replaces the hard-coded k=25 (GLL.py:27);
   * X may carry a leading batch dimension (B x n x d, labels B x base x C or shared):
     B independent graphs in one launch per kernel (SURVEY.md §8f-2), U is B x m x C;
+  * LaplaceLearningSparseHard.ce_loss(X, label_matrix, targets, ...) is apply followed by the
+    callers' custom_ce_loss (losses.py:128-136) and argmax accuracy (FullySup.py:156-171) with
+    one extra kernel (gll_ce_head_batched, DESIGN.md §3.7);
   * label_matrix (floating point), tau and a fixed epsilon are differentiable as well as X
     (the reference returns None for them, GLL.py:177): tau / epsilon may be one-element
     tensors, whose value is read once in the forward (a host sync when on the GPU), and their
@@ -199,96 +202,173 @@ class LaplaceLearningSparseHard(torch.autograd.Function):
         _check_k(k, X.shape[-2])
         return super().apply(X, label_matrix, tau, epsilon, k)
 
+    ce_loss = staticmethod(_ext_mod.ce_loss)
+
+    @classmethod
+    def ce_loss_python(cls, X, label_matrix, targets, tau=0, epsilon="auto", k=DEFAULT_K):
+        """`ce_loss` on the Python torch.autograd.Function path (ctypes onto the same C ABI)."""
+        _check_k(k, X.shape[-2])
+        need = torch.is_grad_enabled() and any(
+            torch.is_tensor(t) and t.requires_grad for t in (X, label_matrix, tau, epsilon))
+        return _CeLossPython.apply(X, label_matrix, targets, tau, epsilon, k, need)
+
     @staticmethod
     def forward(ctx, X, label_matrix, tau=0, epsilon="auto", k=DEFAULT_K):
-        dev = _device_for(X)
-        _poll_status(dev)
-        if X.dim() not in (2, 3) or label_matrix.dim() not in (2, X.dim()):
-            raise ValueError("X must be n x d (or B x n x d), label_matrix base x C "
-                             "(or B x base x C)")
-        B = X.shape[0] if X.dim() == 3 else 1
-        n, d = X.shape[-2:]
-        base, C = label_matrix.shape[-2:]
-        with torch.cuda.device(dev):
-            X32 = _features(X, dev)
-            Y, ydt = _typed(label_matrix, dev)
-            if X.dim() == 3 and Y.dim() == 2:
-                Y = Y.unsqueeze(0).expand(B, base, C).contiguous()   # shared labels
-            if X.dim() == 3 and Y.shape[0] != B:
-                raise ValueError(f"label_matrix batch {Y.shape[0]} != {B}")
-            prob = make_problem(n, d, base, C, k, tau, epsilon)
-            prob.status_sink = _ext_mod.status_sink(dev.index)
-            nbytes = _lib.lib().gll_workspace_bytes(ct.byref(prob))
-            if nbytes == 0:
-                raise ValueError(f"unsupported GLL problem n={n} d={d} base={base} C={C} k={k}")
-            ws = torch.empty(nbytes * B, dtype=torch.uint8, device=dev)
-            U = torch.empty(X.shape[:-2] + (n - base, C), dtype=torch.float64, device=dev)
-            _lib.check(_lib.lib().gll_forward_batched(ct.byref(prob), B, X32.data_ptr(),
-                                                      Y.data_ptr(), ydt, ws.data_ptr(),
-                                                      U.data_ptr(), _stream(dev)),
-                       "gll_forward")
-            _ext_mod.note_call(dev.index)
-        ctx.save_for_backward(X)
-        ctx.prob, ctx.ws, ctx.dev, ctx.B = prob, ws, dev, B
-        # what the label_matrix / tau / epsilon gradients take after: (dtype, device, shape)
-        ctx.like = [(t.dtype, t.device, t.shape) if torch.is_tensor(t) else None
-                    for t in (label_matrix, tau, epsilon)]
-        ctx.Y_shared = X.dim() == 3 and label_matrix.dim() == 2
+        U = _layer_forward(ctx, X, label_matrix, tau, epsilon, k)
         return U if X.is_cuda else U.cpu()
 
     @staticmethod
     def backward(ctx, grad_output):
-        (X,) = ctx.saved_tensors
-        dev, prob = ctx.dev, ctx.prob
+        return (*_layer_backward(ctx, grad_output, ctx.needs_input_grad), None)
+
+
+def _layer_forward(ctx, X, label_matrix, tau, epsilon, k):
+    """The forward of the Python path; returns U on the device and leaves the state of
+    _layer_backward on ctx."""
+    dev = _device_for(X)
+    _poll_status(dev)
+    if X.dim() not in (2, 3) or label_matrix.dim() not in (2, X.dim()):
+        raise ValueError("X must be n x d (or B x n x d), label_matrix base x C "
+                         "(or B x base x C)")
+    B = X.shape[0] if X.dim() == 3 else 1
+    n, d = X.shape[-2:]
+    base, C = label_matrix.shape[-2:]
+    with torch.cuda.device(dev):
+        X32 = _features(X, dev)
+        Y, ydt = _typed(label_matrix, dev)
+        if X.dim() == 3 and Y.dim() == 2:
+            Y = Y.unsqueeze(0).expand(B, base, C).contiguous()   # shared labels
+        if X.dim() == 3 and Y.shape[0] != B:
+            raise ValueError(f"label_matrix batch {Y.shape[0]} != {B}")
+        prob = make_problem(n, d, base, C, k, tau, epsilon)
+        prob.status_sink = _ext_mod.status_sink(dev.index)
+        nbytes = _lib.lib().gll_workspace_bytes(ct.byref(prob))
+        if nbytes == 0:
+            raise ValueError(f"unsupported GLL problem n={n} d={d} base={base} C={C} k={k}")
+        ws = torch.empty(nbytes * B, dtype=torch.uint8, device=dev)
+        U = torch.empty(X.shape[:-2] + (n - base, C), dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().gll_forward_batched(ct.byref(prob), B, X32.data_ptr(),
+                                                  Y.data_ptr(), ydt, ws.data_ptr(),
+                                                  U.data_ptr(), _stream(dev)),
+                   "gll_forward")
+        _ext_mod.note_call(dev.index)
+    ctx.save_for_backward(X)
+    ctx.prob, ctx.ws, ctx.dev, ctx.B = prob, ws, dev, B
+    # what the label_matrix / tau / epsilon gradients take after: (dtype, device, shape)
+    ctx.like = [(t.dtype, t.device, t.shape) if torch.is_tensor(t) else None
+                for t in (label_matrix, tau, epsilon)]
+    ctx.Y_shared = X.dim() == 3 and label_matrix.dim() == 2
+    return U
+
+
+def _layer_backward(ctx, grad_output, need):
+    """gll_backward_batched (+ gll_param_grad_batched) over the workspace on ctx; `need`: which
+    of (X, label_matrix, tau, epsilon) want a gradient.  Returns their four gradients."""
+    (X,) = ctx.saved_tensors
+    dev, prob = ctx.dev, ctx.prob
+    with torch.cuda.device(dev):
+        X32 = _features(X, dev)
+        g, gdt = _typed(grad_output, dev)
+        if gdt == _lib.GLL_DT_I64:
+            g, gdt = g.double(), _lib.GLL_DT_F64
+        gradX = torch.empty(X.shape, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().gll_backward_batched(ct.byref(prob), ctx.B, X32.data_ptr(),
+                                                   ctx.ws.data_ptr(), g.data_ptr(), gdt,
+                                                   gradX.data_ptr(), _stream(dev)),
+                   "gll_backward")
+        what = ((_lib.PG_Y if need[1] and ctx.like[0][0].is_floating_point else 0)
+                | (_lib.PG_TAU if need[2] else 0)
+                | (_lib.PG_EPS if need[3] and prob.eps > 0.0 else 0))
+        gY = gtau = geps = None
+        if what:   # one more pass over the graph the backward just completed
+            B = ctx.B
+            f64 = dict(dtype=torch.float64, device=dev)
+            bufY = torch.empty((B, prob.base, prob.C), dtype=torch.float32, device=dev) \
+                if what & _lib.PG_Y else None
+            btau = torch.empty(B, **f64) if what & _lib.PG_TAU else None
+            beps = torch.empty(B, **f64) if what & _lib.PG_EPS else None
+            scratch = torch.empty(_lib.lib().gll_param_grad_scratch_bytes(ct.byref(prob), B),
+                                  dtype=torch.uint8, device=dev) \
+                if what & (_lib.PG_TAU | _lib.PG_EPS) else None
+
+            def ptr(t):
+                return None if t is None else t.data_ptr()
+
+            _lib.check(_lib.lib().gll_param_grad_batched(ct.byref(prob), B, ctx.ws.data_ptr(),
+                                                         what, ptr(bufY), ptr(btau), ptr(beps),
+                                                         ptr(scratch), _stream(dev)),
+                       "gll_param_grad")
+
+            def like(v, meta):   # the input's dtype, device and shape
+                return v.to(device=meta[1], dtype=meta[0]).reshape(meta[2])
+
+            # batched input: shared labels and the scalars sum over graphs (float64)
+            if bufY is not None:
+                gY = like(bufY.double().sum(0) if ctx.Y_shared else bufY, ctx.like[0])
+            if btau is not None:
+                gtau = like(btau.sum() if B > 1 else btau, ctx.like[1])
+            if beps is not None:
+                geps = like(beps.sum() if B > 1 else beps, ctx.like[2])
+    if not need[0]:
+        gradX = None
+    elif gradX.device != X.device or gradX.dtype != X.dtype:
+        gradX = gradX.to(device=X.device, dtype=X.dtype)
+    return gradX, gY, gtau, geps
+
+
+class _CeLossPython(torch.autograd.Function):
+    """LaplaceLearningSparseHard.ce_loss_python: the layer's Python path followed by
+    gll_ce_head_batched; the backward feeds gbar * grad_loss to the layer's backward."""
+
+    @staticmethod
+    def forward(ctx, X, label_matrix, targets, tau, epsilon, k, need_grad):
+        if not torch.is_tensor(targets) or targets.is_floating_point() or targets.is_complex() \
+                or targets.dtype == torch.bool:
+            raise TypeError("targets must hold integers")
+        U = _layer_forward(ctx, X, label_matrix, tau, epsilon, k)
+        dev, prob, B = ctx.dev, ctx.prob, ctx.B
+        m = prob.n - prob.base
+        lead = tuple(U.shape[:-2])
+        if tuple(targets.shape) != lead + (m,):
+            raise ValueError("targets must have shape "
+                             + (f"B x m = {B} x {m}" if lead else f"m = {m}"))
         with torch.cuda.device(dev):
-            X32 = _features(X, dev)
-            g, gdt = _typed(grad_output, dev)
-            if gdt == _lib.GLL_DT_I64:
-                g, gdt = g.double(), _lib.GLL_DT_F64
-            gradX = torch.empty(X.shape, dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib().gll_backward_batched(ct.byref(prob), ctx.B, X32.data_ptr(),
-                                                       ctx.ws.data_ptr(), g.data_ptr(), gdt,
-                                                       gradX.data_ptr(), _stream(dev)),
-                       "gll_backward")
-            need = ctx.needs_input_grad
-            what = ((_lib.PG_Y if need[1] and ctx.like[0][0].is_floating_point else 0)
-                    | (_lib.PG_TAU if need[2] else 0)
-                    | (_lib.PG_EPS if need[3] and prob.eps > 0.0 else 0))
-            gY = gtau = geps = None
-            if what:   # one more pass over the graph the backward just completed
-                B = ctx.B
-                f64 = dict(dtype=torch.float64, device=dev)
-                bufY = torch.empty((B, prob.base, prob.C), dtype=torch.float32, device=dev) \
-                    if what & _lib.PG_Y else None
-                btau = torch.empty(B, **f64) if what & _lib.PG_TAU else None
-                beps = torch.empty(B, **f64) if what & _lib.PG_EPS else None
-                scratch = torch.empty(_lib.lib().gll_param_grad_scratch_bytes(ct.byref(prob), B),
-                                      dtype=torch.uint8, device=dev) \
-                    if what & (_lib.PG_TAU | _lib.PG_EPS) else None
+            t = targets.detach().to(device=dev, dtype=torch.int64).contiguous()
+            loss = torch.empty(lead, dtype=torch.float64, device=dev)
+            correct = torch.empty(lead, dtype=torch.int64, device=dev)
+            row_loss = torch.empty(lead + (m,), dtype=torch.float64, device=dev)
+            labels = torch.empty(lead + (m,), dtype=torch.int64, device=dev)
+            gbar = torch.empty(U.shape, dtype=torch.float32, device=dev) if need_grad else None
+            sb = _lib.lib().gll_ce_head_scratch_bytes(ct.byref(prob), B)
+            scratch = torch.empty(sb, dtype=torch.uint8, device=dev) if sb else None
+            _lib.check(_lib.lib().gll_ce_head_batched(
+                ct.byref(prob), B, ctx.ws.data_ptr(), t.data_ptr(), loss.data_ptr(),
+                None if gbar is None else gbar.data_ptr(), row_loss.data_ptr(), labels.data_ptr(),
+                correct.data_ptr(), None if scratch is None else scratch.data_ptr(),
+                _stream(dev)), "gll_ce_head")
+        ctx.gbar = gbar
+        out = (loss, U, labels, row_loss, correct)
+        if not X.is_cuda:
+            out = tuple(o.cpu() for o in out)
+        ctx.mark_non_differentiable(*out[1:])
+        return out
 
-                def ptr(t):
-                    return None if t is None else t.data_ptr()
+    @staticmethod
+    def backward(ctx, grad_loss, *_):
+        gl = grad_loss.to(ctx.dev)
+        g = torch.empty_like(ctx.gbar)
+        torch.mul(ctx.gbar, gl.reshape(-1, 1, 1) if ctx.gbar.dim() == 3 else gl.reshape(()), out=g)
+        need = ctx.needs_input_grad
+        gX, gY, gtau, geps = _layer_backward(ctx, g, (need[0], need[1], need[3], need[4]))
+        return gX, gY, None, gtau, geps, None, None
 
-                _lib.check(_lib.lib().gll_param_grad_batched(ct.byref(prob), B, ctx.ws.data_ptr(),
-                                                             what, ptr(bufY), ptr(btau), ptr(beps),
-                                                             ptr(scratch), _stream(dev)),
-                           "gll_param_grad")
 
-                def like(v, meta):   # the input's dtype, device and shape
-                    return v.to(device=meta[1], dtype=meta[0]).reshape(meta[2])
-
-                # batched input: shared labels and the scalars sum over graphs (float64)
-                if bufY is not None:
-                    gY = like(bufY.double().sum(0) if ctx.Y_shared else bufY, ctx.like[0])
-                if btau is not None:
-                    gtau = like(btau.sum() if B > 1 else btau, ctx.like[1])
-                if beps is not None:
-                    geps = like(beps.sum() if B > 1 else beps, ctx.like[2])
-        if not ctx.needs_input_grad[0]:
-            gradX = None
-        elif gradX.device != X.device or gradX.dtype != X.dtype:
-            gradX = gradX.to(device=X.device, dtype=X.dtype)
-        return gradX, gY, gtau, geps, None
+def custom_ce_loss(pred, targets):
+    """The callers' loss in plain torch (losses.py:128-136): -sum(one_hot(targets) *
+    log(pred + 1e-8)) / batch_size for pred m x C with rows that sum to 1.  The yardstick of
+    LaplaceLearningSparseHard.ce_loss, which computes it in one kernel."""
+    onehot = torch.nn.functional.one_hot(targets, num_classes=pred.shape[1]).to(pred.dtype)
+    return -(onehot * torch.log(pred + 1e-8)).sum() / pred.shape[0]
 
 
 # ----------------------------------------------------------------------------------------

@@ -39,14 +39,15 @@ ST_NWORDS = 16
 K_GRAM, K_SELECT, K_FINALIZE, K_CG, K_EDGE, K_GRAD = range(6)
 K_BWD = 6     # cg_grad_fused_kernel
 K_PARAM = 7   # param_grad_kernel: label_matrix / tau / eps gradients
-K_COUNT = 8
+K_LOSS = 8    # ce_head_kernel: cross-entropy head (gll_ce_head_batched)
+K_COUNT = 9
 PG_Y, PG_TAU, PG_EPS = 1, 2, 4   # gll_param_grad_batched `what` bits
 
 # every symbol include/gll.h declares (tests check the library exports all of them)
 EXPORTS = (
     "gll_workspace_bytes", "gll_forward", "gll_backward", "gll_forward_batched",
     "gll_backward_batched", "gll_param_grad_scratch_bytes", "gll_param_grad_batched",
-    "gll_graph", "gll_workspace_view",
+    "gll_ce_head_scratch_bytes", "gll_ce_head_batched", "gll_graph", "gll_workspace_view",
     "gll_cg_csr_workspace_bytes", "gll_cg_csr", "gll_prof_enable", "gll_prof_read",
     "gll_kernel_name", "gll_strerror", "gll_set_knob", "gll_build_id",
 )
@@ -87,6 +88,10 @@ def _declare(lib):
     lib.gll_param_grad_scratch_bytes.restype = sz
     lib.gll_param_grad_batched.argtypes = [P, i32, vp, i32, vp, vp, vp, vp, vp]
     lib.gll_param_grad_batched.restype = i32
+    lib.gll_ce_head_scratch_bytes.argtypes = [P, i32]
+    lib.gll_ce_head_scratch_bytes.restype = sz
+    lib.gll_ce_head_batched.argtypes = [P, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.gll_ce_head_batched.restype = i32
     lib.gll_graph.argtypes = [P, vp, vp, vp]
     lib.gll_graph.restype = i32
     lib.gll_workspace_view.argtypes = [P, vp, ct.POINTER(View)]

@@ -1,6 +1,6 @@
 // api.hip -- the extern "C" boundary declared in include/gll.h.
 //
-// Orchestrates the kernels of knn.hip, rows.hip, solve.hip / gridcg.hip, grad.hip and param_grad.hip on the caller's
+// Orchestrates the kernels of knn.hip, rows.hip, solve.hip / gridcg.hip, grad.hip, param_grad.hip and loss.hip on the caller's
 // stream.  No allocation, no host synchronisation: the caller owns the workspace (the
 // Python mirror takes it from torch's caching allocator) and keeps it alive from
 // gll_forward to gll_backward, as the reference keeps its graph on ctx (GLL.py:69-70).
@@ -153,7 +153,7 @@ size_t static_lds_bytes(const void* fn) {
 static const char* kKernelNames[GLL_K_COUNT] = {
     "gram_d2_kernel", "knn_select_kernel", "row_build_kernel",
     "cg_kernel",      "edge_coef_kernel",  "grad_spmm_kernel", "cg_grad_fused_kernel",
-    "param_grad_kernel"};
+    "param_grad_kernel", "ce_head_kernel"};
 
 static bool vec_ok(const float* X, int d) {
     return (d % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
@@ -342,6 +342,26 @@ int gll_param_grad_batched(const gll_problem* p, int B, void* ws, int what, floa
     Layout L(*p);
     return hip_status(launch_param_grad(L, B, ws, p->eps, what, gradY, grad_tau, grad_eps, scratch,
                                         static_cast<hipStream_t>(stream)));
+}
+
+size_t gll_ce_head_scratch_bytes(const gll_problem* p, int B) {
+    if (check(p) != GLL_OK || B < 1 || B > 65535) return 0;
+    return ce_head_scratch_bytes(p->n - p->base, B);
+}
+
+int gll_ce_head_batched(const gll_problem* p, int B, void* ws, const int64_t* targets,
+                        double* loss, float* gbar, double* row_loss, int64_t* pred_label,
+                        int64_t* correct, void* scratch, void* stream) {
+    int rc = check(p);
+    if (rc != GLL_OK) return rc;
+    if (B < 1 || B > 65535) return GLL_ERR_INVALID_ARG;
+    if (!ws || !loss) return GLL_ERR_INVALID_ARG;
+    const int m = p->n - p->base;
+    if (m > 0 && !targets) return GLL_ERR_INVALID_ARG;
+    if (ce_head_scratch_bytes(m, B) > 0 && !scratch) return GLL_ERR_INVALID_ARG;
+    Layout L(*p);
+    return hip_status(launch_ce_head(L, B, ws, targets, loss, gbar, row_loss, pred_label, correct,
+                                     scratch, static_cast<hipStream_t>(stream)));
 }
 
 int gll_workspace_view(const gll_problem* p, void* ws, gll_view* out) {

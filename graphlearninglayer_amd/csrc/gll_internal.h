@@ -652,5 +652,11 @@ size_t param_grad_scratch_bytes(int n, int B);
 hipError_t launch_param_grad(const Layout& L, int B, void* ws, float eps_fixed, int what,
                              float* gradY, double* grad_tau, double* grad_eps, void* scratch,
                              hipStream_t s);
+// Cross-entropy head over the fp32 predictions a forward left in the workspace (loss.hip):
+// `scratch` ce_head_scratch_bytes(m, B) bytes (0 while a graph's rows fit one workgroup).
+size_t ce_head_scratch_bytes(int m, int B);
+hipError_t launch_ce_head(const Layout& L, int B, void* ws, const int64_t* targets, double* loss,
+                          float* gbar, double* row_loss, int64_t* pred_label, int64_t* correct,
+                          void* scratch, hipStream_t s);
 
 }  // namespace gll

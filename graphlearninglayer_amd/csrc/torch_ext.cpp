@@ -11,6 +11,10 @@
 //     torch::autograd::Function bookkeeping).  The node's backward is gll_backward_batched, plus
 //     one gll_param_grad_batched call when a gradient of label_matrix, tau or epsilon is wanted
 //     (the reference returns None for them, GLL.py:177);
+//   * `ce_loss(X, label_matrix, targets, tau=0, epsilon='auto', k=25)` is the same call followed
+//     by the cross-entropy head (gll_ce_head_batched: custom_ce_loss of losses.py:128-136 and the
+//     argmax accuracy of FullySup.py:156-171 in one kernel); its node is the same one, holding
+//     the head's dloss/dU;
 //   * the device status words (tiny eps, CG non-convergence, grid-barrier failure) accumulate in
 //     a sticky per-device sink that is copied to pinned memory every kFlushEvery calls and turned
 //     into the reference's warnings (GLL.py:240-241, 273-274) at a later call, with no host sync.
@@ -263,6 +267,7 @@ struct LaplaceBackward : public torch::autograd::Node {
     int n_inputs_ = 1;
     GradLike Y_, tau_, eps_;
     bool Y_shared_ = false;   // 2-D label_matrix with batched X: the gradient sums over graphs
+    at::Tensor gbar_;         // ce_loss: dloss/dU (fp32, U's shape); the node's output is the loss
 
     std::string name() const override { return "LaplaceLearningSparseHardBackward"; }
 
@@ -270,6 +275,7 @@ struct LaplaceBackward : public torch::autograd::Node {
         std::lock_guard<std::mutex> lk(mutex_);
         X_.reset_data();
         ws_.reset();
+        gbar_.reset();
     }
 
     variable_list apply(variable_list&& grads) override {
@@ -281,6 +287,11 @@ struct LaplaceBackward : public torch::autograd::Node {
         c10::DeviceGuard guard(dev);
         at::Tensor X32 = features(X, dev);
         at::Tensor g = grads[0].device() == dev ? grads[0] : grads[0].to(dev);
+        if (gbar_.defined()) {   // ce_loss: dL/dU = gbar * dL/dloss, broadcast over the graphs
+            const at::Tensor gl = gbar_.dim() == 3 ? g.reshape({-1, 1, 1}) : g.reshape({});
+            g = at::empty_like(gbar_);
+            at::mul_out(g, gbar_, gl);
+        }
         if (g.scalar_type() != at::kFloat && g.scalar_type() != at::kDouble) g = g.to(at::kDouble);
         if (!g.is_contiguous()) g = g.contiguous();
         const int gcode = g.scalar_type() == at::kFloat ? GLL_DT_F32 : GLL_DT_F64;
@@ -404,34 +415,55 @@ const at::Tensor& tensor_arg(PyObject* o, const char* what) {
     return THPVariable_Unpack(o);
 }
 
-PyObject* apply_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames) {
-    static const char* names[] = {"X", "label_matrix", "tau", "epsilon", "k"};
-    PyObject* a[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (nargs > 5) raise_py(PyExc_TypeError, "apply() takes at most 5 arguments");
+// Positional / keyword arguments of a METH_FASTCALL entry into `a` (one slot per name).
+void collect_args(const char* fn, const char* const* names, int nn, PyObject* const* args,
+                  Py_ssize_t nargs, PyObject* kwnames, PyObject** a) {
+    if (nargs > nn)
+        raise_py(PyExc_TypeError, std::string(fn) + "() takes at most " + std::to_string(nn) +
+                                      " arguments");
     for (Py_ssize_t q = 0; q < nargs; ++q) a[q] = args[q];
     if (kwnames) {
         const Py_ssize_t nk = PyTuple_GET_SIZE(kwnames);
         for (Py_ssize_t q = 0; q < nk; ++q) {
             const char* kn = PyUnicode_AsUTF8(PyTuple_GET_ITEM(kwnames, q));
             int slot = -1;
-            for (int t = 0; t < 5 && kn; ++t)
+            for (int t = 0; t < nn && kn; ++t)
                 if (std::strcmp(kn, names[t]) == 0) slot = t;
             if (slot < 0 || a[slot])
-                raise_py(PyExc_TypeError, std::string("apply() got an unexpected or repeated "
-                                                      "keyword argument '") + (kn ? kn : "?") + "'");
+                raise_py(PyExc_TypeError, std::string(fn) + "() got an unexpected or repeated "
+                                              "keyword argument '" + (kn ? kn : "?") + "'");
             a[slot] = args[nargs + q];
         }
     }
-    if (!a[0] || !a[1]) raise_py(PyExc_TypeError, "apply() needs X and label_matrix");
-    const at::Tensor& X = tensor_arg(a[0], "X");
-    const at::Tensor& Y = tensor_arg(a[1], "label_matrix");
-    at::Tensor tau_t, eps_t;   // defined where tau / epsilon came as tensors
+}
+
+// One forward of the layer, shared by apply and ce_loss: argument checks, marshalling, the
+// workspace, gll_forward_batched on the current stream and the status bookkeeping.  The device
+// guard lives as long as the call does.
+struct LayerCall {
+    at::Tensor X, Y, tau_t, eps_t;   // the inputs as given (tau_t / eps_t: defined where tensors)
+    at::Tensor X32, ws, U;
+    gll_problem p{};
+    int64_t B = 1, n = 0, base = 0, C = 0;
+    bool batched = false;
+    int devi = 0;
+    hipStream_t s = nullptr;
+    c10::OptionalDeviceGuard guard;
+};
+
+void layer_forward(LayerCall& c, const char* fn, PyObject* aX, PyObject* aY, PyObject* atau,
+                   PyObject* aeps, PyObject* ak) {
+    if (!aX || !aY) raise_py(PyExc_TypeError, std::string(fn) + "() needs X and label_matrix");
+    c.X = tensor_arg(aX, "X");
+    c.Y = tensor_arg(aY, "label_matrix");
+    const at::Tensor& X = c.X;
+    const at::Tensor& Y = c.Y;
     double tau = 0.0;
-    if (a[2] && !scalar_tensor_arg(a[2], "tau", tau_t, tau)) tau = parse_float(a[2], "tau");
-    const double eps = a[3] ? parse_eps(a[3], eps_t) : 0.0;
+    if (atau && !scalar_tensor_arg(atau, "tau", c.tau_t, tau)) tau = parse_float(atau, "tau");
+    const double eps = aeps ? parse_eps(aeps, c.eps_t) : 0.0;
     int64_t k = kDefaultK;
-    if (a[4]) {
-        k = PyLong_AsLongLong(a[4]);
+    if (ak) {
+        k = PyLong_AsLongLong(ak);
         if (k == -1 && PyErr_Occurred()) {
             PyErr_Clear();
             raise_py(PyExc_TypeError, "k must be an int");
@@ -456,12 +488,12 @@ PyObject* apply_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames)
         devi = c10::hip::current_device();
     }
     const c10::Device dev(c10::kCUDA, devi);
-    c10::DeviceGuard guard(dev);
+    c.guard.reset_device(dev);
     DeviceStatus& st = status_of(devi);
     if (!st.order.empty()) poll(st, false);
     const bool batched = X.dim() == 3;
     const int64_t B = batched ? X.size(0) : 1;
-    at::Tensor X32 = features(X, dev);
+    c.X32 = features(X, dev);
     at::Tensor Yd = Y.device() == dev ? Y : Y.detach().to(dev);
     const int ycode = dtype_code(Yd);
     if (batched && Y.dim() == 2) Yd = Yd.unsqueeze(0).expand({B, base, C});   // shared labels
@@ -469,46 +501,128 @@ PyObject* apply_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames)
         raise_py(PyExc_ValueError, "label_matrix batch " + std::to_string(Yd.size(0)) +
                                        " != " + std::to_string(B));
     if (!Yd.is_contiguous()) Yd = Yd.contiguous();
-    gll_problem p = make_problem(n, d, base, C, k, tau, eps, st.sink.data_ptr<int32_t>());
-    const size_t nb = gll_workspace_bytes(&p);
+    c.p = make_problem(n, d, base, C, k, tau, eps, st.sink.data_ptr<int32_t>());
+    const size_t nb = gll_workspace_bytes(&c.p);
     if (nb == 0)
         raise_py(PyExc_ValueError, "unsupported GLL problem n=" + std::to_string(n) + " d=" +
                                        std::to_string(d) + " base=" + std::to_string(base) +
                                        " C=" + std::to_string(C) + " k=" + std::to_string(k));
-    const auto opts = X32.options();
-    at::Tensor ws = at::empty({int64_t(nb) * B}, opts.dtype(at::kByte));
-    at::Tensor U = batched ? at::empty({B, n - base, C}, opts.dtype(at::kDouble))
-                           : at::empty({n - base, C}, opts.dtype(at::kDouble));
-    const hipStream_t s = current_stream(devi);
-    check_rc(gll_forward_batched(&p, int(B), X32.data_ptr<float>(), Yd.data_ptr(), ycode,
-                                 ws.data_ptr(), U.data_ptr<double>(), s),
+    const auto opts = c.X32.options();
+    c.ws = at::empty({int64_t(nb) * B}, opts.dtype(at::kByte));
+    c.U = batched ? at::empty({B, n - base, C}, opts.dtype(at::kDouble))
+                  : at::empty({n - base, C}, opts.dtype(at::kDouble));
+    c.s = current_stream(devi);
+    check_rc(gll_forward_batched(&c.p, int(B), c.X32.data_ptr<float>(), Yd.data_ptr(), ycode,
+                                 c.ws.data_ptr(), c.U.data_ptr<double>(), c.s),
              "gll_forward");
-    after_call(st, devi, s);
-    std::vector<at::Tensor> inputs{X, Y};
-    if (tau_t.defined()) inputs.push_back(tau_t);
-    if (eps_t.defined()) inputs.push_back(eps_t);
-    if (torch::autograd::compute_requires_grad(inputs)) {
-        auto node = std::shared_ptr<LaplaceBackward>(new LaplaceBackward(),
-                                                     torch::autograd::deleteNode);
-        node->set_next_edges(torch::autograd::collect_next_edges(inputs));
-        node->n_inputs_ = int(inputs.size());
-        node->Y_.set(1, Y);
-        node->Y_shared_ = batched && Y.dim() == 2;
-        if (tau_t.defined()) node->tau_.set(2, tau_t);
-        if (eps_t.defined()) node->eps_.set(tau_t.defined() ? 3 : 2, eps_t);
-        node->X_ = torch::autograd::SavedVariable(X, false);
-        node->ws_ = std::move(ws);
-        node->p_ = p;
-        node->B_ = B;
-        node->diag_ = g_grad_diag;
-        torch::autograd::set_history(U, node);
-    }
-    return THPVariable_Wrap(X.is_cuda() ? std::move(U) : U.cpu());
+    after_call(st, devi, c.s);
+    c.B = B;
+    c.n = n;
+    c.base = base;
+    c.C = C;
+    c.batched = batched;
+    c.devi = devi;
 }
 
-PyObject* apply_py(PyObject*, PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames) {
+std::vector<at::Tensor> grad_inputs(const LayerCall& c) {
+    std::vector<at::Tensor> inputs{c.X, c.Y};
+    if (c.tau_t.defined()) inputs.push_back(c.tau_t);
+    if (c.eps_t.defined()) inputs.push_back(c.eps_t);
+    return inputs;
+}
+
+// The autograd node of a completed forward (it takes the workspace over).
+std::shared_ptr<LaplaceBackward> make_node(LayerCall& c, const std::vector<at::Tensor>& inputs) {
+    auto node = std::shared_ptr<LaplaceBackward>(new LaplaceBackward(),
+                                                 torch::autograd::deleteNode);
+    node->set_next_edges(torch::autograd::collect_next_edges(inputs));
+    node->n_inputs_ = int(inputs.size());
+    node->Y_.set(1, c.Y);
+    node->Y_shared_ = c.batched && c.Y.dim() == 2;
+    if (c.tau_t.defined()) node->tau_.set(2, c.tau_t);
+    if (c.eps_t.defined()) node->eps_.set(c.tau_t.defined() ? 3 : 2, c.eps_t);
+    node->X_ = torch::autograd::SavedVariable(c.X, false);
+    node->ws_ = std::move(c.ws);
+    node->p_ = c.p;
+    node->B_ = c.B;
+    node->diag_ = g_grad_diag;
+    return node;
+}
+
+PyObject* apply_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames) {
+    static const char* names[] = {"X", "label_matrix", "tau", "epsilon", "k"};
+    PyObject* a[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    collect_args("apply", names, 5, args, nargs, kwnames, a);
+    LayerCall c;
+    layer_forward(c, "apply", a[0], a[1], a[2], a[3], a[4]);
+    const std::vector<at::Tensor> inputs = grad_inputs(c);
+    if (torch::autograd::compute_requires_grad(inputs))
+        torch::autograd::set_history(c.U, make_node(c, inputs));
+    return THPVariable_Wrap(c.X.is_cuda() ? std::move(c.U) : c.U.cpu());
+}
+
+// ------------------------------------------------------------------------------------------
+// ce_loss(X, label_matrix, targets, tau=0, epsilon='auto', k=25): the layer and the
+// cross-entropy head its callers put behind it (losses.py:128-136, FullySup.py:156-171) in one
+// call.  gll_ce_head_batched reads the predictions the forward left in the workspace and writes
+// loss, row losses, predicted labels, the correct count and -- when a gradient is wanted --
+// dloss/dU, which the node keeps: its backward is the layer's, fed gbar * grad_loss.
+// ------------------------------------------------------------------------------------------
+PyObject* ce_loss_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames) {
+    static const char* names[] = {"X", "label_matrix", "targets", "tau", "epsilon", "k"};
+    PyObject* a[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    collect_args("ce_loss", names, 6, args, nargs, kwnames, a);
+    if (!a[2]) raise_py(PyExc_TypeError, "ce_loss() needs targets");
+    const at::Tensor& T = tensor_arg(a[2], "targets");
+    if (!at::isIntegralType(T.scalar_type(), false))
+        raise_py(PyExc_TypeError, "targets must hold integers");
+    LayerCall c;
+    layer_forward(c, "ce_loss", a[0], a[1], a[3], a[4], a[5]);
+    const int64_t m = c.n - c.base;
+    const bool shape_ok = c.batched ? (T.dim() == 2 && T.size(0) == c.B && T.size(1) == m)
+                                    : (T.dim() == 1 && T.size(0) == m);
+    if (!shape_ok)
+        raise_py(PyExc_ValueError, std::string("targets must have shape ") +
+                                       (c.batched ? "B x m = " + std::to_string(c.B) + " x " : "m = ") +
+                                       std::to_string(m));
+    const c10::Device dev(c10::kCUDA, c.devi);
+    at::Tensor Td = T.detach().to(dev, at::kLong).contiguous();
+    const auto f64 = c.X32.options().dtype(at::kDouble);
+    const auto i64 = c.X32.options().dtype(at::kLong);
+    const std::vector<int64_t> one = c.batched ? std::vector<int64_t>{c.B} : std::vector<int64_t>{};
+    const std::vector<int64_t> rows = c.batched ? std::vector<int64_t>{c.B, m} : std::vector<int64_t>{m};
+    at::Tensor loss = at::empty(one, f64), correct = at::empty(one, i64);
+    at::Tensor row_loss = at::empty(rows, f64), labels = at::empty(rows, i64);
+    const std::vector<at::Tensor> inputs = grad_inputs(c);
+    const bool need_grad = torch::autograd::compute_requires_grad(inputs);
+    at::Tensor gbar, scratch;
+    if (need_grad) gbar = at::empty(c.U.sizes(), c.X32.options());
+    const size_t sb = gll_ce_head_scratch_bytes(&c.p, int(c.B));
+    if (sb) scratch = at::empty({int64_t(sb)}, c.X32.options().dtype(at::kByte));
+    check_rc(gll_ce_head_batched(&c.p, int(c.B), c.ws.data_ptr(), Td.data_ptr<int64_t>(),
+                                 loss.data_ptr<double>(),
+                                 need_grad ? gbar.data_ptr<float>() : nullptr,
+                                 row_loss.data_ptr<double>(), labels.data_ptr<int64_t>(),
+                                 correct.data_ptr<int64_t>(),
+                                 sb ? scratch.data_ptr() : nullptr, c.s),
+             "gll_ce_head");
+    if (need_grad) {
+        auto node = make_node(c, inputs);
+        node->gbar_ = std::move(gbar);
+        torch::autograd::set_history(loss, node);
+    }
+    at::Tensor out[5] = {loss, c.U, labels, row_loss, correct};
+    PyObject* tup = PyTuple_New(5);
+    if (!tup) throw PyErrSet{};
+    for (int q = 0; q < 5; ++q)
+        PyTuple_SET_ITEM(tup, q, THPVariable_Wrap(c.X.is_cuda() ? out[q] : out[q].cpu()));
+    return tup;
+}
+
+template <PyObject* (*Impl)(PyObject* const*, Py_ssize_t, PyObject*)>
+PyObject* entry_py(PyObject*, PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames) {
     try {
-        return apply_impl(args, nargs, kwnames);
+        return Impl(args, nargs, kwnames);
     } catch (const PyErrSet&) {
         return nullptr;
     } catch (const c10::Error& e) {
@@ -521,12 +635,21 @@ PyObject* apply_py(PyObject*, PyObject* const* args, Py_ssize_t nargs, PyObject*
 }
 
 PyMethodDef kApplyDef = {
-    "apply", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(apply_py)),
+    "apply", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(entry_py<apply_impl>)),
     METH_FASTCALL | METH_KEYWORDS,
     "U = LaplaceLearningSparseHard.apply(X, label_matrix, tau=0, epsilon='auto', k=25)\n"
     "(GLL.py:14; k: neighbours incl. self, the reference hard-codes 25).  X, a floating-point\n"
     "label_matrix and tau / a fixed epsilon given as one-element tensors are differentiable\n"
     "(a tensor's value is read once in the forward: a host sync when it lives on the GPU)"};
+
+PyMethodDef kCeLossDef = {
+    "ce_loss", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(entry_py<ce_loss_impl>)),
+    METH_FASTCALL | METH_KEYWORDS,
+    "loss, pred, pred_labels, row_loss, correct =\n"
+    "    LaplaceLearningSparseHard.ce_loss(X, label_matrix, targets, tau=0, epsilon='auto', k=25)\n"
+    "apply followed by custom_ce_loss (losses.py:128-136) and the argmax accuracy\n"
+    "(FullySup.py:156-171) with one extra kernel.  Only loss is differentiable (with respect to\n"
+    "the inputs apply differentiates); a target outside [0, C) leaves its row out"};
 
 // ------------------------------------------------------------------------------------------
 // status API for the Python layer
@@ -546,6 +669,8 @@ PYBIND11_MODULE(_gll_torch, m) {
     m.doc() = "LaplaceLearningSparseHard.apply over libgll.so (include/gll.h) and its status sink";
     m.add_object("apply", pybind11::reinterpret_steal<pybind11::object>(
                               PyCFunction_NewEx(&kApplyDef, nullptr, m.attr("__name__").ptr())));
+    m.add_object("ce_loss", pybind11::reinterpret_steal<pybind11::object>(
+                                PyCFunction_NewEx(&kCeLossDef, nullptr, m.attr("__name__").ptr())));
     m.def("status_sink", [](int dev) { return int64_t(status_of(dev).sink.data_ptr()); },
           "device address of the sticky status words of device `dev` (gll_problem.status_sink)");
     m.def("note_call", [](int dev) {

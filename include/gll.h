@@ -172,6 +172,30 @@ int gll_param_grad_batched(const gll_problem* p, int B, void* workspace, int wha
                            float* gradY, double* grad_tau, double* grad_eps,
                            void* scratch, void* stream);
 
+/* Cross-entropy head: replaces custom_ce_loss (losses.py:128-136) and the argmax accuracy its
+ * callers take next to it (FullySup.py:156-171), read from the fp32 predictions gll_forward
+ * left in the workspace (gll_view.U32; the float64 U is exactly double(U32)).  With m = n - base,
+ * t_i = targets[g*m + i] and everything evaluated in float64:
+ *   p_i        = double(U32[i, t_i]) + 1e-8
+ *   row_loss_i = -log(p_i)               no clamp: p_i <= 0 gives the NaN / inf PyTorch gives
+ *   loss[g]    = (sum_i row_loss_i) / m
+ *   gbar[i, c] = float(-(1/m) / p_i) at c == t_i, 0 elsewhere   (= dloss/dU: fp32 m x C, dense,
+ *                                                  what gll_backward_batched takes as GLL_DT_F32)
+ *   pred_label_i = lowest index among the maxima of row i; correct[g] = #{i: pred_label_i == t_i}
+ * A target outside [0, C) masks its row (the way to leave rows out): row_loss 0, a zero gbar
+ * row, never counted as correct, U never indexed with it; the divisor stays m, as
+ * custom_ce_loss divides by batch_size.  Call after gll_forward(_batched) on the same
+ * workspace(s) and problem.  targets: B x m int64; loss: B float64; gbar: B x m x C fp32;
+ * row_loss: B x m float64; pred_label: B x m int64; correct: B int64 -- all device memory, all but
+ * targets and loss may be NULL.  `scratch`: gll_ce_head_scratch_bytes(p, B) bytes (0 for
+ * m <= 4096: one launch, grid = B; past that a row pass plus a reduce).  The sum runs in a fixed
+ * order that depends on (m, C) alone: no atomics, bitwise reproducible, and graph g of a batch
+ * equals the single call.  m == 0 writes loss = 0 and nothing else. */
+size_t gll_ce_head_scratch_bytes(const gll_problem* p, int B);
+int gll_ce_head_batched(const gll_problem* p, int B, void* workspace, const int64_t* targets,
+                        double* loss, float* gbar, double* row_loss, int64_t* pred_label,
+                        int64_t* correct, void* scratch, void* stream);
+
 /* Graph only (the device half of knn_sym_dist, GLL.py:180-244): kNN search, symmetric
  * CSR, eps, weights and degrees into the workspace; no solve.  Requires p->base == 0
  * (no labeled block; size the workspace for that problem).  Read the arrays with
@@ -225,7 +249,8 @@ int gll_cg_csr(int m, int C, const int32_t* row_ptr, const int32_t* col, const f
                            * (single small graphs, fixed eps) */
 #define GLL_K_PARAM 7     /* param_grad_kernel (+ param_reduce_kernel): label_matrix / tau / eps
                            * gradients (gll_param_grad_batched) */
-#define GLL_K_COUNT 8
+#define GLL_K_LOSS 8      /* ce_head_kernel: cross-entropy head (gll_ce_head_batched) */
+#define GLL_K_COUNT 9
 int gll_prof_enable(int kid, int period);
 int gll_prof_read(int kid, double* ms_total, int* count);
 const char* gll_kernel_name(int kid);
