@@ -5,13 +5,19 @@
 // column runs its own PCG with per-column step sizes, and a column is frozen once it meets
 // its tolerance (GLL.py:258-268 masks alpha/beta the same way).
 //
-// cg_gv_kernel (round 3, the default): pipelined PCG (Ghysels & Vanroose 2014, Alg. 4) --
-// ONE grid barrier per iteration.  Before the barrier a workgroup publishes m = M w for its
-// rows together with its partial dot products (r,u), (w,u), (r,r); after it, the SpMV
-// n = A m gathers the published m while the partials are summed, and every vector update is
-// local.  The workgroup's slice of the matrix (column byte offsets and values) is staged in
-// LDS once per solve, so an iteration reads nothing from global memory but the one published
-// vector and the partials.  Rows past the LDS capacity read their entries from the CSR.
+// cg_gv_kernel (round 3, the default), two forms on one machinery.  MODE 1, what every solve
+// runs: Chronopoulos-Gear single-reduction PCG, two grid barriers per iteration (u = M r
+// published, then the partial dot products (r,u), (w,u), (r,r)).  MODE 0, no longer dispatched:
+// pipelined PCG (Ghysels & Vanroose 2014, Alg. 4) -- ONE grid barrier per iteration: before it a
+// workgroup publishes m = M w with its partials; after it, the SpMV n = A m gathers the
+// published m while the partials are summed, and every vector update is local.  Its four extra
+// recurrences cost fp32 accuracy: the true residual of a Luu solve at m = 2100 ended at
+// 4-9e-6 ||b|| under rtol 1e-6 (tests/test_gpu_cg_contract.py), so the Luu solves left it for
+// MODE 1 (stress step 0.673 -> 0.720 ms, profiles/cg01_bench_ab.txt); the form stays in the
+// kernel for the barrier work DESIGN.md §9 names, which must pass that test to come back.
+// The workgroup's slice of the matrix (column byte offsets and values) is staged in LDS once
+// per solve, so an iteration reads nothing from global memory but the published vector and the
+// partials.  Rows past the LDS capacity read their entries from the CSR.
 //
 // cg_grid_classic_kernel (rounds 1-2): classic two-reduction PCG, two grid barriers per
 // iteration, matrix entries and two vectors (z, p) gathered from global memory every iteration;
@@ -1337,11 +1343,12 @@ template <class Mat>
 static hipError_t dispatch_grid(const Mat& A, const GridCgArgs& a, int64_t nnz, float* ws,
                                 bool oversub, hipStream_t s) {
     if (!oversub) {
-        // Luu solves (rtol 1e-6 relative): pipelined; general CSR (utils.laplace's refinement
-        // sweeps on ill-conditioned systems): Chronopoulos-Gear
-        hipError_t e;
-        if constexpr (Mat::kSeparateDiag) e = dispatch_gv<Mat, 0>(A, a, nnz, ws, s);
-        else e = dispatch_gv<Mat, 1>(A, a, nnz, ws, s);
+        // Chronopoulos-Gear for the Luu solves as for the general CSR.  The pipelined form's
+        // extra recurrences (w, z, s, q) let the true residual drift away from the recursive one
+        // the stop test reads: at m = 2100 (22-24 iterations, rtol 1e-6) it returned
+        // ||b - Luu x|| = 4.0-9.2e-6 ||b|| where textbook fp32 PCG and every other kernel reach
+        // 1.0-1.2e-6 (tests/test_gpu_cg_contract.py, profiles/cg01_gpu_tests.txt).
+        const hipError_t e = dispatch_gv<Mat, 1>(A, a, nnz, ws, s);
         if (e != hipErrorNotSupported) return e;
     }
     return dispatch_classic(A, a, nnz < 0 ? int64_t(a.m) * 8 : nnz, ws, oversub, s);

@@ -33,7 +33,11 @@ extern "C" {
 #define GLL_DT_F64 1
 #define GLL_DT_I64 2
 
-/* status words the device writes into the workspace (read with gll_status_offset) */
+/* status words the device writes into the workspace (gll_view.status).  gll_forward zeroes the
+ * block's words; the solves then atomicMax / atomicAdd into them, so the adjoint words of several
+ * gll_backward calls on one workspace accumulate until the next forward.  A column that hits
+ * max_iter keeps its last iterate (U / wadj hold the x after max_iter updates); converging on
+ * iteration max_iter itself counts as converged. */
 #define GLL_ST_TINY_EPS 0      /* eps_i < 1e-10 seen (GLL.py:240-241 warns) */
 #define GLL_ST_FWD_NONCONV 1   /* forward CG columns that hit max_iter */
 #define GLL_ST_FWD_ITERS 2     /* max forward CG iterations over columns */
@@ -223,8 +227,13 @@ int gll_workspace_view(const gll_problem* p, void* workspace, gll_view* out);
  * stable_conjgrad, GLL.py:247-276, as used by utils.laplace, utils.py:589).
  * A: m x m CSR (row_ptr m+1, col, val) fp32; b, x: m x C row-major fp32 (x is output).
  * Stops per column when ||r_c||_2 <= atol (absolute, like stable_conjgrad's tol) or
- * max_iter.  `iters` (device int, may be NULL) receives the max iteration count,
- * `nonconv` (device int, may be NULL) the columns that hit max_iter.  `workspace`
+ * max_iter (0 => 100000); a column with ||b_c||_2 <= atol takes 0 iterations and x_c = 0.  A
+ * column that hits max_iter returns its last iterate in x_c (the x after max_iter updates), not
+ * zero and not NaN.  `iters` and `nonconv` (device ints, may be NULL) ACCUMULATE: the kernels
+ * atomicMax the largest per-column iteration count into `iters` and atomicAdd the number of
+ * columns that hit max_iter into `nonconv`, so the caller zeroes both before the call (or keeps
+ * them as running maximum / sum over several calls); converging on iteration max_iter itself
+ * counts as converged.  `workspace`
  * (gll_cg_csr_workspace_bytes) holds the Krylov vectors: required when m > 2048 (those
  * systems run on the whole GPU as one ordinary launch sized within the co-resident
  * workgroup capacity, C <= 16; a lost grid barrier is rescued by one workgroup solving
