@@ -49,7 +49,7 @@ EXPORTS = (
     "gll_backward_batched", "gll_param_grad_scratch_bytes", "gll_param_grad_batched",
     "gll_ce_head_scratch_bytes", "gll_ce_head_batched", "gll_graph", "gll_workspace_view",
     "gll_cg_csr_workspace_bytes", "gll_cg_csr", "gll_prof_enable", "gll_prof_read",
-    "gll_kernel_name", "gll_strerror", "gll_set_knob", "gll_build_id",
+    "gll_kernel_name", "gll_strerror", "gll_set_knob", "gll_build_id", "gll_select_route",
 )
 
 
@@ -106,6 +106,8 @@ def _declare(lib):
     lib.gll_prof_read.restype = i32
     lib.gll_kernel_name.argtypes = [i32]
     lib.gll_kernel_name.restype = ct.c_char_p
+    lib.gll_select_route.argtypes = [ct.POINTER(Problem), i32, i32, i32, ct.POINTER(ct.c_int32)]
+    lib.gll_select_route.restype = i32
     lib.gll_set_knob.argtypes = [i32, i32]
     lib.gll_set_knob.restype = i32
     lib.gll_strerror.argtypes = [i32]

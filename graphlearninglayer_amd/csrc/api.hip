@@ -1,7 +1,7 @@
 // api.hip -- the extern "C" boundary declared in include/gll.h.
 //
-// Orchestrates the kernels of knn.hip, rows.hip, solve.hip / gridcg.hip, grad.hip, param_grad.hip and loss.hip on the caller's
-// stream.  No allocation, no host synchronisation: the caller owns the workspace (the
+// Orchestrates the kernels of gram.hip, select.hip, order.hip, rows.hip, solve.hip / gridcg.hip,
+// grad.hip, param_grad.hip and loss.hip on the caller's stream.  No allocation, no host synchronisation: the caller owns the workspace (the
 // Python mirror takes it from torch's caching allocator) and keeps it alive from
 // gll_forward to gll_backward, as the reference keeps its graph on ctx (GLL.py:69-70).
 #include <atomic>
@@ -11,7 +11,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "gll_internal.h"
+#include "knn_route.h"
 
 namespace gll {
 
@@ -452,6 +452,27 @@ const char* gll_kernel_name(int kid) {
     return kKernelNames[kid];
 }
 
+int gll_select_route(const gll_problem* p, int B, int x_aligned, int rows,
+                     int32_t out[GLL_SEL_ROUTE_WORDS]) {
+    int rc = check(p);
+    if (rc != GLL_OK) return rc;
+    if (B < 1 || B > 65535 || !out) return GLL_ERR_INVALID_ARG;
+    Layout L(*p);
+    // rows: a panel of the problem's row panels (one graph), or all n
+    if (L.PR < L.n ? (B > 1 || rows < 1 || rows > L.PR) : rows != L.n) return GLL_ERR_INVALID_ARG;
+    Batch bt;
+    bt.B = B;
+    const SelRoute rt = select_route(L, bt, x_aligned && p->d % 4 == 0, 0, rows);
+    const SelVariant& v = rt.v;
+    const SelWideVariant& w = rt.w;
+    const int32_t words[GLL_SEL_ROUTE_WORDS] = {
+        rt.wide, rt.wide ? w.V : v.KC, rt.wide ? w.NP : v.V, rt.wide ? w.CAP : v.NP,
+        rt.wide ? w.KMX : v.PG, rt.wide ? w.TOP : v.NU, v.XQ, v.R, v.CH, v.H,
+        select_table_index(rt), select_table_rows()};
+    for (int q = 0; q < GLL_SEL_ROUTE_WORDS; ++q) out[q] = words[q];
+    return words[10] >= 0 ? GLL_OK : GLL_ERR_UNSUPPORTED;
+}
+
 #ifndef GLL_BUILD_ID
 #define GLL_BUILD_ID "unknown"
 #endif
@@ -471,21 +492,25 @@ const char* gll_strerror(int code) {
 
 #ifdef GLL_TRACE
 // Diagnostic build only (libgll_trace.so): in-kernel timestamps per translation unit
-// (0 knn, 1 rows, 2 solve, 3 grad), see GLL_TRACE_UNIT in gll_internal.h.
+// (0 knn = gram.hip, 1 rows, 2 solve, 3 grad, 4 gridcg, 5 select), see GLL_TRACE_UNIT in
+// gll_internal.h.
 namespace gll {
 void trace_read_knn(unsigned long long*);
 void trace_read_rows(unsigned long long*);
 void trace_read_solve(unsigned long long*);
 void trace_read_grad(unsigned long long*);
 void trace_read_gridcg(unsigned long long*);
+void trace_read_select(unsigned long long*);
 void trace_reset_gridcg();
 void trace_read_wg_knn(unsigned long long*);
 void trace_read_wg_solve(unsigned long long*);
 void trace_read_wg_gridcg(unsigned long long*);
+void trace_read_wg_select(unsigned long long*);
 void trace_reset_knn();
 void trace_reset_rows();
 void trace_reset_solve();
 void trace_reset_grad();
+void trace_reset_select();
 }  // namespace gll
 
 extern "C" int gll_trace_read(int unit, unsigned long long* out) {
@@ -496,6 +521,7 @@ extern "C" int gll_trace_read(int unit, unsigned long long* out) {
         case 2: gll::trace_read_solve(out); return GLL_OK;
         case 3: gll::trace_read_grad(out); return GLL_OK;
         case 4: gll::trace_read_gridcg(out); return GLL_OK;
+        case 5: gll::trace_read_select(out); return GLL_OK;
         default: return GLL_ERR_INVALID_ARG;
     }
 }
@@ -506,6 +532,7 @@ extern "C" int gll_trace_read_wg(int unit, unsigned long long* out) {
         case 0: gll::trace_read_wg_knn(out); return GLL_OK;
         case 2: gll::trace_read_wg_solve(out); return GLL_OK;
         case 4: gll::trace_read_wg_gridcg(out); return GLL_OK;
+        case 5: gll::trace_read_wg_select(out); return GLL_OK;
         default: return GLL_ERR_INVALID_ARG;
     }
 }
@@ -525,6 +552,7 @@ extern "C" int gll_trace_reset(int unit) {
         case 2: gll::trace_reset_solve(); return GLL_OK;
         case 3: gll::trace_reset_grad(); return GLL_OK;
         case 4: gll::trace_reset_gridcg(); return GLL_OK;
+        case 5: gll::trace_reset_select(); return GLL_OK;
         default: return GLL_ERR_INVALID_ARG;
     }
 }

@@ -210,7 +210,7 @@ struct Layout {
     size_t fsync;     // fused backward: [0] solved columns, [32] finished gradient blocks,
                       // [64] poison (a lost solve: the counters may be stale), [96] release
                       // (set by the last column to arrive; the gradient blocks poll it)
-    size_t d2s;       // float: the fp16 D2 scale of the pre-split GEMM (knn.hip tile_d2_scale)
+    size_t d2s;       // float: the fp16 D2 scale of the pre-split GEMM (gram.hip tile_d2_scale)
     size_t pid, perm; // locality order (order_rows): nearest pivot of each row, the row order
     size_t ohist;     // locality order: rows per pivot of each 64-row block ([ceil(n/64)][64])
 
@@ -272,7 +272,7 @@ struct Layout {
         xlo = take(size_t(n) * dp * 2);
         xnrm = take(size_t(n) * 4);
         fsync = take(512);   // four words on their own 128-B lines, zeroed by row_build
-        d2s = take(256);     // fp16 D2 scale of the pre-split Gram (knn.hip tile_d2_scale)
+        d2s = take(256);     // fp16 D2 scale of the pre-split Gram (gram.hip tile_d2_scale)
         pid = take(size_t(n) * 4);
         perm = take(size_t(n) * 4);
         ohist = take(size_t((n + 63) / 64) * 64 * 4);
@@ -597,7 +597,7 @@ hipError_t launch_select(const Layout& L, const Batch& bt, void* ws, const float
                          hipStream_t s, int r0 = 0, int rows = -1);
 hipError_t launch_gram_panel(const Layout& L, void* ws, const float* X, bool vec, int r0, int rows,
                              hipStream_t s);
-// Locality order of the rows of one large graph (knn.hip order_rows): rows grouped by their
+// Locality order of the rows of one large graph (order.hip launch_order): rows grouped by their
 // nearest of kPiv pivot rows under the Gram distances, so each XCD's share of the select and of
 // the chunked gradient is a run of rows whose neighbours mostly lie in the same run -- the X rows
 // those kernels gather then stay in that XCD's 4 MB L2 instead of streaming from the MALL.  Speed

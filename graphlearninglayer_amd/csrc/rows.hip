@@ -7,7 +7,7 @@
 //   * reverse entries: every l that listed i (pushed by knn_select_kernel onto i's reverse
 //     list, spilling to the overflow list past RCAP); a reverse entry already in i's own list
 //     (a mutual pair) keeps max(d_ij, d_ji): the union-max of GLL.py:197.  (The two
-//     distances agree bitwise unless one row refined its ranking in float64, knn.hip);
+//     distances agree bitwise unless one row refined its ranking in float64, select.hip);
 //   * the row is staged in LDS (global scratch for hub rows), rank-sorted by column --
 //     deterministic whatever order the atomics produced -- and written to its slot
 //     (row_start, row_len; hub rows take a bump-allocated range);

@@ -96,9 +96,9 @@ extern "C" {
 #define GLL_KNOB_VR_RV 0      /* balanced CG: virtual rows per thread (4 / 8 / 10) */
 #define GLL_KNOB_GRID_CAP 1   /* whole-GPU CG: co-resident workgroup capacity */
 #define GLL_KNOB_GRAM_TILE 2  /* pre-split Gram: 128- or 256-row tiles */
-#define GLL_KNOB_SEL_FORM 3   /* kNN select form: 1 latency (PG 2), 2 occupancy (knn.hip) */
+#define GLL_KNOB_SEL_FORM 3   /* kNN select form: 1 latency (PG 2), 2 occupancy (knn_route.h select_route) */
 #define GLL_KNOB_GRAM_TAIL 4  /* 256-tile Gram's short last round: 1 none, 2 as 128-subtiles
-                               * instead of 64-subtiles (knn.hip) */
+                               * instead of 64-subtiles (gram.hip launch_gram) */
 #define GLL_KNOB_ROW_PRE 5    /* row build label prefetch: 1 on, 2 off (rows.hip) */
 #define GLL_KNOB_COUNT 6
 int gll_set_knob(int knob, int value);
@@ -263,6 +263,17 @@ int gll_cg_csr(int m, int C, const int32_t* row_ptr, const int32_t* col, const f
 int gll_prof_enable(int kid, int period);
 int gll_prof_read(int kid, double* ms_total, int* count);
 const char* gll_kernel_name(int kid);
+
+/* Diagnostic: which instantiation of the kNN select a launch over `rows` rows (p->n, or one of
+ * the problem's row panels) of each of B graphs runs, x_aligned saying whether X is 16-B
+ * aligned.  No HIP call: it runs without a GPU.  out[0] = 1 for knn_select_wide_kernel, whose
+ * template arguments (V, NP, CAP, KMX, TOP) are out[1..5]; 0 for knn_select_kernel, whose
+ * (KC, V, NP, PG, NU, XQ, R, CH, H) are out[1..9]; out[10] = the variant's row in the table
+ * of instantiated kernels (-1, and GLL_ERR_UNSUPPORTED, when it has none: the launch would
+ * fail), out[11] = the table's length.  Reads GLL_KNOB_SEL_FORM. */
+#define GLL_SEL_ROUTE_WORDS 12
+int gll_select_route(const gll_problem* p, int B, int x_aligned, int rows,
+                     int32_t out[GLL_SEL_ROUTE_WORDS]);
 
 /* Build identity: sha256 (16 hex) of the sources, headers and flags this library was built
  * from (graphlearninglayer_amd/build.py source_digest).  bench.py cites only profiles

@@ -180,7 +180,7 @@ def test_split_phase_gram_shapes(n, d, eps):
                                      (130, 128, "auto"), (300, 2, 1.0)])
 def test_half_tile_gram_shapes(n, d, eps):
     """Single graphs with d <= 128 and fewer than 512 64-tiles take the 512-thread half tile
-    (knn.hip gram_bf3h_kernel): FullySup's shape, a scalar-load ragged shape (777 x 37), the
+    (gram.hip gram_bf3h_kernel): FullySup's shape, a scalar-load ragged shape (777 x 37), the
     largest triangle on this route (31 tiles a side: 496), d = 125 (lanes past d in the last
     feature group), two tiles of which one nearly empty (130) and d = 2 (unit rows on a circle;
     at d = 1 every row is +-1, all ties).  Exact kNN sets against float64 and U / grad_X
@@ -201,7 +201,7 @@ def test_half_tile_gram_shapes(n, d, eps):
 @pytest.mark.parametrize("k,eps", [(13, 1.0), (14, "auto"), (29, 1.0), (30, "auto"),
                                    (57, 1.0), (57, "auto")])
 def test_candidate_capacity_boundaries(k, eps):
-    """k at each edge of the select's candidate capacity (knn.hip launch_select: the smallest of
+    """k at each edge of the select's candidate capacity (select.hip launch_select: the smallest of
     16 / 32 / 64 keeping a re-rank margin >= 4, so 13 | 14 and 29 | 30 switch lists; k = 57 is
     the largest k include/gll.h accepts): exact kNN sets
     and U / grad_X against the oracle, fixed and automatic eps (GLL.py:183, utils.py:574)."""
@@ -1169,7 +1169,7 @@ def test_knn_row_panels_automatic_past_the_n2_buffer():
 @pytest.mark.parametrize("cfg,B,scale", [("ns", 8, 1.0), ("ns", 8, 1e3), ("ns", 8, 1e-3),
                                            ("fullysup", 8, 1.0), ("stress", 2, 1.0)])
 def test_fp16_distance_storage_matches_fp32(cfg, B, scale):
-    """Batches on the pre-split Gram route store D2 as fp16 x 2^e (knn.hip dput): every GEMM tile
+    """Batches on the pre-split Gram route store D2 as fp16 x 2^e (gram.hip dput): every GEMM tile
     recomputes e itself from the graph's row norms (a max-reduction over nrm, |x - x_0|^2) and
     stores it as a plain word -- the same value from every tile, nothing carried over from an
     earlier call -- so features scaled by 1e3 or 1e-3 stay in range, and a workspace reused by a
@@ -1220,7 +1220,7 @@ def test_batched_bench_route_matches_oracle_every_graph():
     """The exact route bench.py's `batched` line times (B = 64 NS graphs, fixed eps, tau 0.07):
     B x C = 640 column solves > 256 CUs, so the per-column CG runs 256 threads x 2 rows with the
     single-reduction recurrence (solve.hip cg_dispatch); the distances are stored fp16 x 2^e and
-    the Gram takes the pre-split route (knn.hip d2_half, gram_tile256).  Every graph's U and
+    the Gram takes the pre-split route (knn_route.h d2_half, gram_tile256).  Every graph's U and
     grad_X against the float64 oracle at the 1e-4 bar (GLL.py:53,93,146-159), the oracle fed each
     graph's own GPU kNN lists."""
     from graphlearninglayer_amd.synth import seeded_gbar
@@ -1268,7 +1268,7 @@ def test_chunked_grad_matches_row_kernel_bitwise(cfg, eps):
 
 @pytest.mark.parametrize("d", [100, 37, 256])
 def test_presplit_gram_matches_inline_split(d):
-    """The 128-tile Gram on pre-split hi/lo planes with LDS-DMA staging (knn.hip gram_split_kernel
+    """The 128-tile Gram on pre-split hi/lo planes with LDS-DMA staging (gram.hip gram_split_kernel
     + gram_pk_kernel, the default for batches and for large graphs with d > 128) against the
     inline-split kernel (GLL_FLAG_GRAM_INLINE): both only nominate candidates, so the kNN (exact
     against float64) and every output agree bitwise; ragged n (not a multiple of 128) and d (not
@@ -1287,7 +1287,7 @@ def test_presplit_gram_matches_inline_split(d):
         assert ncp == 0
         np.testing.assert_array_equal(Up, Ui)
         return
-    # single graphs with d <= 128 take the inline kernel (knn.hip launch_gram); batches keep the
+    # single graphs with d <= 128 take the inline kernel (gram.hip launch_gram); batches keep the
     # pre-split one: a batch of two (this graph and a second) against the single calls, at the
     # batched-parity bar (the batched launch runs a different CG configuration)
     GLL = _gll()
@@ -1386,7 +1386,7 @@ def test_fused_backward_handoff_with_uneven_column_solves(live):
                                              ("ns", 2, 37, 100), ("ns", 26, 0, None),
                                              ("ns", 26, 37, 100), ("ns", 64, 0, None)])
 def test_gram_256_tiles_match_128_tiles(cfg, B, n_extra, d, monkeypatch):
-    """The 256-tile pre-split Gram (knn.hip gram_pk2_kernel, 8 waves) against the 128-tile one
+    """The 256-tile pre-split Gram (gram.hip gram_pk2_kernel, 8 waves) against the 128-tile one
     (gram_pk_kernel) on batches, ragged n and d included: the same k order and epilogue, so U
     and grad_X agree bitwise (the GLL_KNOB_GRAM_TILE test knob forces either).  B = 26 (n 1,000
     and 1,037): 260 256-tiles on a 256-CU device, whose short last round runs as 64-subtiles (the
@@ -1734,3 +1734,81 @@ def test_utils_laplace_wide_knn_num(knn_num):
         d2 = np.sum((X64 - X64[i]) ** 2, axis=1)
         order = np.argsort(d2, kind="stable")
         assert set(ind[i].tolist()) == set(order[:knn_num].tolist()), i
+
+
+def _select_point_id(pt):
+    return "n{}-d{}-K{}-B{}-panel{}-form{}".format(*pt)
+
+
+def _check_exact_lists(X, ind, d2, k):
+    """The float64 kNN sets in every row (no row excused past the 1e-12 tie gap, and the point
+    list holds no such tie: tests/test_lib_cpu.py), ordered by (d^2, index) with self first."""
+    assert O.knn_set_mismatch(X, ind, k, rel_gap=1e-12) == []
+    assert (ind[:, 0] == np.arange(ind.shape[0])).all() and (d2[:, 0] == 0).all()
+    dd, di = d2[:, 1:], ind[:, 1:]
+    assert (np.diff(dd, axis=1) >= 0).all()
+    # equal fp32 distances: by index, unless the float64 distances the select ranked by differ
+    X64 = X.astype(np.float64)
+    for i, r in zip(*np.nonzero((np.diff(dd, axis=1) == 0) & (np.diff(di, axis=1) < 0))):
+        a, b = (np.sum((X64[i] - X64[di[i, r + q]]) ** 2) for q in (0, 1))
+        assert a < b, (i, r)
+
+
+@pytest.mark.parametrize("pt", __import__("tests.select_points", fromlist=["POINTS"]).POINTS,
+                         ids=_select_point_id)
+def test_every_select_variant_is_exact(pt):
+    """One small problem per row of the select's table of instantiated kernels (select.hip;
+    tests/select_points.py lists them and the CPU suite proves the list reaches every row).
+    Single graphs: the float64 kNN sets, ordered lists.  Batches (the rows with fp16 distance
+    storage among them): every graph's lists, distances and eps, read from its workspace block,
+    are bitwise those of the single-graph call on that graph's rows under GLL_FLAG_D2_F32, and
+    the float64 sets."""
+    import ctypes as ct
+    from graphlearninglayer_amd import _lib
+    from tests import select_points as SP
+    n, d, k, B, panel, form = pt
+    Xs = SP.features(n, d, B)
+    GLL = _gll()
+    if B == 1:
+        try:
+            _lib.set_knob(_lib.KNOB_SEL_FORM, form)
+            g = GLL.device_graph(torch.from_numpy(Xs[0]).cuda(), k, "auto",
+                                 flags=_lib.FLAG_KNN_PANEL if panel else 0)
+            ind, d2 = g["knn_idx"].cpu().numpy(), g["knn_d2"].cpu().numpy()
+        finally:
+            _lib.set_knob(_lib.KNOB_SEL_FORM, 0)
+        _check_exact_lists(Xs[0], ind, d2, k)
+        return
+    base, C = 8, 2
+    prob = GLL.make_problem(n, d, base, C, k, 0.07, "auto")
+    prob.max_iter = 2   # the solve is not what this test reads
+    lib = _lib.lib()
+    wb = lib.gll_workspace_bytes(ct.byref(prob))
+    ws = torch.empty(B * wb, dtype=torch.uint8, device="cuda")
+    U = torch.empty(B, n - base, C, dtype=torch.float64, device="cuda")
+    Xd = torch.from_numpy(np.stack(Xs)).cuda()
+    Yd = torch.zeros(B, base, C, dtype=torch.float32, device="cuda")
+    Yd[:, :, 0] = 1.0
+    _lib.check(lib.gll_forward_batched(ct.byref(prob), B, Xd.data_ptr(), Yd.data_ptr(),
+                                       _lib.GLL_DT_F32, ws.data_ptr(), U.data_ptr(),
+                                       torch.cuda.current_stream().cuda_stream),
+               "gll_forward_batched")
+    torch.cuda.synchronize()
+    K = prob.K
+    for g in range(B):
+        view = _lib.View()
+        _lib.check(lib.gll_workspace_view(ct.byref(prob), ws.data_ptr() + g * wb, ct.byref(view)),
+                   "gll_workspace_view")
+
+        def arr(ptr, count, dtype):
+            off = ptr - ws.data_ptr()
+            return ws[off: off + 4 * count].view(dtype).cpu().numpy()
+
+        ind = arr(view.knn_idx, n * K, torch.int32).reshape(n, K)
+        d2 = arr(view.knn_d2, n * K, torch.float32).reshape(n, K)
+        eps = arr(view.eps, n, torch.float32)
+        one = GLL.device_graph(Xd[g], k, "auto", flags=_lib.FLAG_D2_F32)
+        np.testing.assert_array_equal(ind, one["knn_idx"].cpu().numpy())
+        np.testing.assert_array_equal(d2, one["knn_d2"].cpu().numpy())
+        np.testing.assert_array_equal(eps, one["eps"].cpu().numpy())
+        _check_exact_lists(Xs[g], ind, d2, k)

@@ -53,7 +53,7 @@ def test_workspace_bytes_and_validation():
     p = G.make_problem(1000, 512, 500, 10, 10, 0.07, 1.0)
     nb = lib.gll_workspace_bytes(ct.byref(p))
     # dominated by the n x n squared-distance planes (two at NS: the split-phase Gram) and the
-    # n x d hi/lo bf16 planes of the pre-split Gram (knn.hip gram_split_kernel)
+    # n x d hi/lo bf16 planes of the pre-split Gram (gram.hip gram_split_kernel)
     assert 2 * 1000 * 1000 * 4 < nb < 2 * 1000 * 1000 * 4 + 1000 * 512 * 4 + 4 * 2**20
     bad = G.make_problem(1000, 512, 500, 10, 10, 0.07, 1.0)
     bad.K = 1
@@ -219,3 +219,46 @@ def test_product_library_reads_no_switch_but_debug():
                          check=True).stdout
     names = sorted(set(re.findall(r"\bGLL_[A-Z0-9_]+", out)))
     assert names == ["GLL_DEBUG"], names
+
+
+def test_select_route_table_is_complete_and_minimal():
+    """The kNN select launches through a table of instantiated variants (select.hip); a variant
+    select_route (knn_route.h) can return and the table lacks is a launch that fails, and a row
+    nothing reaches is dead device code.  gll_select_route reports, without a GPU, the row a
+    problem takes: over the sweep below every supported problem has a row, and the rows reached
+    are all of them.  The one-problem-per-row list the GPU test runs (tests/select_points.py)
+    reaches every row too, and none of its graphs has a row whose (K-1)-th and K-th neighbours
+    lie within the 1e-12 tie gap, so the GPU test excuses nothing."""
+    import itertools
+
+    from tests import select_points as SP
+    S = SP.SWEEP
+    reached, length, supported = set(), None, 0
+    for n, d, K, B, al, panel, flags, form in itertools.product(
+            S["n"], S["d"], S["K"], S["B"], S["aligned"], S["panel"], S["flags"], S["form"]):
+        r = SP.route(n, d, K, B, al, panel, flags, form)
+        if r is None:
+            continue
+        rc, out = r
+        assert rc == 0 and out[10] >= 0, (n, d, K, B, al, panel, flags, form, rc, out)
+        supported += 1
+        length = out[11]
+        reached.add(out[10])
+    assert supported > 50_000
+    assert reached == set(range(length)), sorted(set(range(length)) - reached)
+    rows = set()
+    for n, d, K, B, panel, form in SP.POINTS:
+        rc, out = SP.route(n, d, K, B, 1, panel, 0, form)
+        assert rc == 0, (n, d, K, B, panel, form)
+        rows.add(out[10])
+    assert rows == set(range(length)) and len(SP.POINTS) == length
+    shapes = {}
+    for n, d, K, B, panel, form in SP.POINTS:
+        shapes.setdefault((n, d, B), set()).add(K)
+    ties = {}
+    for (n, d, B), Ks in shapes.items():
+        for g, X in enumerate(SP.features(n, d, B)):
+            for K, t in SP.tie_rows(X, sorted(Ks)).items():
+                if t:
+                    ties[(n, d, K, g)] = t[:4]
+    assert ties == {}

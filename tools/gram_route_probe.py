@@ -1,6 +1,6 @@
 """Forward time of one large single graph with the pre-split Gram (default for d > 128) and the
 inline 128-tile Gram (GLL_FLAG_GRAM_INLINE), at sizes past the stress shape (diagnostic, GPU box):
-decides whether the single-graph routing in knn.hip launch_gram needs an n bound as well."""
+decides whether the single-graph routing in gram.hip launch_gram needs an n bound as well."""
 import ctypes as ct
 import os
 import sys

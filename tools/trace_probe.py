@@ -24,8 +24,11 @@ lib = ct.CDLL(_tl if os.path.exists(_tl) else
               os.path.join(ROOT, "graphlearninglayer_amd", "_obj", "libgll_trace.so"))
 lib.gll_workspace_bytes.restype = ct.c_size_t
 lib.gll_trace_read.argtypes = [ct.c_int, ct.POINTER(ct.c_ulonglong)]
-UNITS = {0: ("knn", ["gram", "select", "gram_wide", "gram48", "gram_bf3"]), 1: ("rows", ["row_build"]),
-         2: ("solve", ["cg_ell", "cg_lds", "cg_csr"]), 3: ("grad", ["edge_coef", "grad_spmm"])}
+# unit -> (name, kernels by GLL_TRACE_SCOPE index; "" = an index the unit does not use).  Unit 0 is
+# gram.hip (it keeps the symbols of the former knn unit), unit 5 select.hip.
+UNITS = {0: ("knn", ["gram", "", "gram_wide", "gram48", "gram_bf3"]), 1: ("rows", ["row_build"]),
+         2: ("solve", ["cg_ell", "cg_lds", "cg_csr"]), 3: ("grad", ["edge_coef", "grad_spmm"]),
+         5: ("select", ["", "select"])}
 CG_PTS = ["entry", "ell loaded+P", "ovf compacted", "rz/bb reduced", "it1 spmv", "it1 pAp",
           "it1 rr", "it1 P published", "loop done", "stored"]
 
@@ -95,6 +98,7 @@ def timeline(tr, label):
     if g[21] and g[22] and g[14] > g[10]:
         mhz = (g[22] - g[21]) / ((g[14] - g[10]) / 100.0)
         print(f"gram block 0: shader clock {mhz:.0f} MHz (s_memtime / s_memrealtime)")
+    g = tr[5].astype(np.int64)
     if g[16] and g[20]:
         print("select wave 0: " + ", ".join(f"{nm} +{TICK_US * (g[q] - g[20]):.2f}" for q, nm in
                                            [(23, "row loaded"), (16, "scanned"), (17, "merged"), (18, "refined"),
