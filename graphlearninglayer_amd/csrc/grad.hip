@@ -62,8 +62,7 @@ static void launch_edge_coef(const EdgeArgs& a, const Batch& bt, int lpr, hipStr
     const unsigned rows = 4u * unsigned(kWave / lpr);
     const dim3 grid((unsigned(a.n) + rows - 1) / rows, bt.B);
     if (lpr == 16) launch_k(edge_coef_kernel<CV, 16>, grid, 256, 0, s, a);
-    else if (lpr == 32) launch_k(edge_coef_kernel<CV, 32>, grid, 256, 0, s, a);
-    else launch_k(edge_coef_kernel<CV, 64>, grid, 256, 0, s, a);
+    else launch_k(edge_coef_kernel<CV, 32>, grid, 256, 0, s, a);
 }
 
 // out_i = sum_e coef_e (x_i - x_{col_e}) in the difference form: translation-invariant like the
@@ -292,9 +291,9 @@ static hipError_t grad_nd(const EdgeArgs& a, const Batch& bt, const float* X, fl
     dim3 grid((a.n + 3) / 4, bt.B);
     const int nd = (a.d + 255) / 256;
 #define GLL_GRAD(ND)                                                                        \
-    do {                                                                                    \
+    do {   /* WIDE only up to ND = 4: wider rows have no such instantiation */              \
         if (bt.B == 1 && ND <= 4)                                                           \
-            launch_k(grad_spmm_kernel<AUTO, ND, VEC, true, CV>, grid, 256, 0, s, a, X, out, bt.x, bt.gx);  \
+            launch_k(grad_spmm_kernel<AUTO, ND, VEC, (ND <= 4), CV>, grid, 256, 0, s, a, X, out, bt.x, bt.gx);  \
         else                                                                                \
             launch_k(grad_spmm_kernel<AUTO, ND, VEC, false, CV>, grid, 256, 0, s, a, X, out, bt.x, bt.gx); \
     } while (0)

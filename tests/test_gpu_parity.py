@@ -1030,10 +1030,18 @@ def test_balanced_cg_vrm_clamp_at_wide_k_matches_oracle():
     assert O.rel_err(gr, O.backward(st, g)) <= TOL
 
 
-def _fwd_bwd_c_abi(X, Y, k, tau, eps, gbar, flags=0, bwd_flags=None, ws_fill=None):
-    """gll_forward + gll_backward through ctypes with explicit problem flags: (U, grad_X).
-    `bwd_flags`: the backward's own flags (default: the forward's); `ws_fill`: a byte value the
-    workspace holds before the forward (default: torch.empty's contents)."""
+def _nan(*shape, dtype):
+    """An output buffer no kernel has written: NaN everywhere (a caching-allocator block from
+    torch.empty usually still holds the previous, correct result of the same shape)."""
+    return torch.full(shape, float("nan"), dtype=dtype, device="cuda")
+
+
+def _fwd_bwd_c_abi(X, Y, k, tau, eps, gbar, flags=0, bwd_flags=None, ws_fill=None, counts=False):
+    """gll_forward + gll_backward through ctypes with explicit problem flags: (U, grad_X), both
+    written into NaN-filled buffers.  `bwd_flags`: the backward's own flags (default: the
+    forward's); `ws_fill`: a byte value the workspace holds before the forward (default:
+    torch.empty's contents); `counts`: also return the backward's launches
+    (tests/launch_counts.py)."""
     import ctypes as ct
     from graphlearninglayer_amd import _lib
     GLL = _gll()
@@ -1046,24 +1054,30 @@ def _fwd_bwd_c_abi(X, Y, k, tau, eps, gbar, flags=0, bwd_flags=None, ws_fill=Non
     ws = torch.empty(lib.gll_workspace_bytes(ct.byref(prob)), dtype=torch.uint8, device="cuda")
     if ws_fill is not None:
         ws.fill_(ws_fill)
-    U = torch.empty(n - base, C, dtype=torch.float64, device="cuda")
-    gx = torch.empty(n, d, dtype=torch.float32, device="cuda")
+    U = _nan(n - base, C, dtype=torch.float64)
+    gx = _nan(n, d, dtype=torch.float32)
     Xd = torch.from_numpy(np.ascontiguousarray(X)).cuda()
     Yd = torch.from_numpy(np.ascontiguousarray(Y)).cuda()
     gd = torch.from_numpy(np.ascontiguousarray(gbar, dtype=np.float64)).cuda()
     s = torch.cuda.current_stream().cuda_stream
     _lib.check(lib.gll_forward(ct.byref(prob), Xd.data_ptr(), Yd.data_ptr(), _lib.GLL_DT_F32,
                                ws.data_ptr(), U.data_ptr(), s), "gll_forward")
-    _lib.check(lib.gll_backward(ct.byref(bprob), Xd.data_ptr(), Yd.data_ptr(), _lib.GLL_DT_F32,
-                                ws.data_ptr(), gd.data_ptr(), _lib.GLL_DT_F64, gx.data_ptr(), s),
-               "gll_backward")
+    import contextlib
+    from tests.launch_counts import counted
+    with (counted() if counts else contextlib.nullcontext()) as got:
+        _lib.check(lib.gll_backward(ct.byref(bprob), Xd.data_ptr(), Yd.data_ptr(),
+                                    _lib.GLL_DT_F32, ws.data_ptr(), gd.data_ptr(),
+                                    _lib.GLL_DT_F64, gx.data_ptr(), s), "gll_backward")
     torch.cuda.synchronize()
+    if counts:
+        return U.cpu().numpy(), gx.cpu().numpy(), got
     return U.cpu().numpy(), gx.cpu().numpy()
 
 
 def _fwd_bwd_batched_c_abi(Xs, Ys, k, tau, eps, G, flags=0, ws=None):
-    """gll_forward_batched + gll_backward_batched through ctypes: (U[B], grad_X[B]).  `ws`: a
-    workspace to reuse (default: a fresh torch.empty one)."""
+    """gll_forward_batched + gll_backward_batched through ctypes: (U[B], grad_X[B]), both
+    written into NaN-filled buffers.  `ws`: a workspace to reuse (default: a fresh torch.empty
+    one)."""
     import ctypes as ct
     from graphlearninglayer_amd import _lib
     GLL = _gll()
@@ -1075,8 +1089,8 @@ def _fwd_bwd_batched_c_abi(Xs, Ys, k, tau, eps, G, flags=0, ws=None):
     if ws is None:
         ws = torch.empty(B * wb, dtype=torch.uint8, device="cuda")
     assert ws.numel() >= B * wb
-    U = torch.empty(B, n - base, C, dtype=torch.float64, device="cuda")
-    gx = torch.empty(B, n, d, dtype=torch.float32, device="cuda")
+    U = _nan(B, n - base, C, dtype=torch.float64)
+    gx = _nan(B, n, d, dtype=torch.float32)
     Xd = torch.from_numpy(np.ascontiguousarray(Xs)).cuda()
     Yd = torch.from_numpy(np.ascontiguousarray(Ys)).cuda()
     gd = torch.from_numpy(np.ascontiguousarray(G, dtype=np.float64)).cuda()
@@ -1255,8 +1269,20 @@ def test_chunked_grad_matches_row_kernel_bitwise(cfg, eps):
     X, lab = synth(c["base"], c["batch"], c["d"], r=c["r"], seed=6)
     Y = one_hot(lab[: c["base"]])
     g = seeded_gbar(c["batch"], 10, 3)
-    Uc, gc = _fwd_bwd_c_abi(X, Y, c["k"], 0.07, eps, g, flags=_lib.FLAG_GRAD_CHUNK)
-    Ur, gr = _fwd_bwd_c_abi(X, Y, c["k"], 0.07, eps, g, flags=_lib.FLAG_GRAD_ROWS)
+    Uc, gc, ran_c = _fwd_bwd_c_abi(X, Y, c["k"], 0.07, eps, g, flags=_lib.FLAG_GRAD_CHUNK,
+                                   counts=True)
+    Ur, gr, ran_r = _fwd_bwd_c_abi(X, Y, c["k"], 0.07, eps, g, flags=_lib.FLAG_GRAD_ROWS,
+                                   counts=True)
+    # the two sides ran different kernels: the edge pass + grad_chunk_kernel against the whole-row
+    # form (grad_spmm_kernel, or at NS with fixed eps the fused backward's gradient role)
+    from tests import grad_ref
+    shape = (c["base"] + c["batch"], c["d"], c["base"], 10, c["k"], 1, eps == "auto", True)
+    want_c = grad_ref.route(*shape, _lib.FLAG_GRAD_CHUNK)
+    want_r = grad_ref.route(*shape, _lib.FLAG_GRAD_ROWS)
+    assert want_c.family == "chunk" and want_r.family == (
+        "fused" if (cfg, eps) == ("ns", 1.0) else "spmm")
+    assert ran_c.counts == want_c.counts == (1, 1, 0, 1), ran_c
+    assert ran_r.counts == want_r.counts, ran_r
     np.testing.assert_array_equal(Uc, Ur)
     np.testing.assert_array_equal(gc, gr)
     if cfg == "stress":   # the chunked kernel's automatic case; the oracle check runs elsewhere
@@ -1300,8 +1326,10 @@ def test_presplit_gram_matches_inline_split(d):
     assert O.rel_err(Ub[1], U2) <= 1e-5
 
 
-def _fwd_bwds_c_abi(X, Y, k, tau, eps, gbar, flags=0, backward_calls=1):
-    """gll_forward then `backward_calls` x gll_backward on ONE workspace through ctypes."""
+def _fwd_bwds_c_abi(X, Y, k, tau, eps, gbar, flags=0, backward_calls=1, counts=False):
+    """gll_forward then `backward_calls` x gll_backward on ONE workspace through ctypes, every
+    output NaN-filled before its call: (U, [grad_X], status words) and, with `counts`, the
+    launches of each backward (tests/launch_counts.py)."""
     import ctypes as ct
     from graphlearninglayer_amd import _lib
     GLL = _gll()
@@ -1310,21 +1338,27 @@ def _fwd_bwds_c_abi(X, Y, k, tau, eps, gbar, flags=0, backward_calls=1):
     prob = GLL.make_problem(n, d, base, C, k, tau, eps, flags=flags)
     lib = _lib.lib()
     ws = torch.empty(lib.gll_workspace_bytes(ct.byref(prob)), dtype=torch.uint8, device="cuda")
-    U = torch.empty(n - base, C, dtype=torch.float64, device="cuda")
+    U = _nan(n - base, C, dtype=torch.float64)
     Xd = torch.from_numpy(np.ascontiguousarray(X)).cuda()
     Yd = torch.from_numpy(np.ascontiguousarray(Y)).cuda()
     Gd = torch.from_numpy(np.ascontiguousarray(gbar)).cuda()
     s = torch.cuda.current_stream().cuda_stream
     _lib.check(lib.gll_forward(ct.byref(prob), Xd.data_ptr(), Yd.data_ptr(), _lib.GLL_DT_F32,
                                ws.data_ptr(), U.data_ptr(), s), "gll_forward")
-    grads = []
+    import contextlib
+    from tests.launch_counts import counted
+    grads, launches = [], []
     for _ in range(backward_calls):
-        gx = torch.empty(n, d, dtype=torch.float32, device="cuda")
-        _lib.check(lib.gll_backward(ct.byref(prob), Xd.data_ptr(), None, 0, ws.data_ptr(),
-                                    Gd.data_ptr(), _lib.GLL_DT_F64, gx.data_ptr(), s),
-                   "gll_backward")
+        gx = _nan(n, d, dtype=torch.float32)
+        with (counted() if counts else contextlib.nullcontext()) as got:
+            _lib.check(lib.gll_backward(ct.byref(prob), Xd.data_ptr(), None, 0, ws.data_ptr(),
+                                        Gd.data_ptr(), _lib.GLL_DT_F64, gx.data_ptr(), s),
+                       "gll_backward")
         grads.append(gx.cpu().numpy())
+        launches.append(got.counts if counts else None)
     st = ws[: 4 * _lib.ST_NWORDS].view(torch.int32).cpu().tolist()
+    if counts:
+        return U.cpu().numpy(), grads, st, launches
     return U.cpu().numpy(), grads, st
 
 
@@ -1335,15 +1369,24 @@ def test_fused_backward_equals_two_launches_bitwise(cfg):
     launches (GLL_FLAG_BWD_UNFUSED): bitwise equal, and equal again on a second backward over
     the same workspace (the hand-off counters re-arm); against the float64 oracle at 1e-4.
     The gradient waves take the rows in class order (round 6); `wide_base`
-    (3,500 labeled + 500 unlabeled rows at d = 128) sorts 63 64-row chunks."""
+    (1,400 labeled + 500 unlabeled rows at d = 128) sorts 30 64-row chunks in 248 workgroups,
+    the most the 256 CUs hold co-resident (at 3,500 + 500 rows the launch needs 510, the fused
+    kernel declines and both sides of this comparison would be the two-launch path).  Which
+    side ran which kernels is asserted from the bracketed launches."""
     from graphlearninglayer_amd import _lib
     from graphlearninglayer_amd.synth import CONFIGS, one_hot, seeded_gbar, synth
-    c = CONFIGS[cfg] if cfg in CONFIGS else dict(base=3500, batch=500, d=128, k=10, r=1.0)
+    c = CONFIGS[cfg] if cfg in CONFIGS else dict(base=1400, batch=500, d=128, k=10, r=1.0)
     X, lab = synth(c["base"], c["batch"], c["d"], r=c["r"], seed=6)
     Y = one_hot(lab[: c["base"]])
     g = seeded_gbar(c["batch"], 10, 17)
-    Uf, gf, stf = _fwd_bwds_c_abi(X, Y, c["k"], 0.07, 1.0, g, backward_calls=3)
-    Uu, gu, stu = _fwd_bwds_c_abi(X, Y, c["k"], 0.07, 1.0, g, flags=_lib.FLAG_BWD_UNFUSED)
+    Uf, gf, stf, ran_f = _fwd_bwds_c_abi(X, Y, c["k"], 0.07, 1.0, g, backward_calls=3,
+                                         counts=True)
+    Uu, gu, stu, ran_u = _fwd_bwds_c_abi(X, Y, c["k"], 0.07, 1.0, g, flags=_lib.FLAG_BWD_UNFUSED,
+                                         counts=True)
+    # (edge pass, gradient, fused backward, CG) launches: one fused launch per backward against
+    # a CG and a gradient launch
+    assert ran_f == [(0, 0, 1, 0)] * 3, ran_f
+    assert ran_u == [(0, 1, 0, 1)], ran_u
     np.testing.assert_array_equal(Uf, Uu)
     for gx in gf:
         np.testing.assert_array_equal(gx, gu[0])
@@ -1371,8 +1414,12 @@ def test_fused_backward_handoff_with_uneven_column_solves(live):
     full = seeded_gbar(c["batch"], 10, 23)
     for q, col in enumerate(live):
         g[:, col] = full[:, col] * 10.0 ** (3 * q)   # scales 1, 1e3, 1e6
-    Uf, gf, stf = _fwd_bwds_c_abi(X, Y, c["k"], 0.07, 1.0, g, backward_calls=3)
-    Uu, gu, stu = _fwd_bwds_c_abi(X, Y, c["k"], 0.07, 1.0, g, flags=_lib.FLAG_BWD_UNFUSED)
+    Uf, gf, stf, ran_f = _fwd_bwds_c_abi(X, Y, c["k"], 0.07, 1.0, g, backward_calls=3,
+                                         counts=True)
+    Uu, gu, stu, ran_u = _fwd_bwds_c_abi(X, Y, c["k"], 0.07, 1.0, g, flags=_lib.FLAG_BWD_UNFUSED,
+                                         counts=True)
+    assert ran_f == [(0, 0, 1, 0)] * 3, ran_f      # the fused kernel, every backward
+    assert ran_u == [(0, 1, 0, 1)], ran_u          # a CG launch and a gradient launch
     for gx in gf:
         np.testing.assert_array_equal(gx, gu[0])
     assert stf[_lib.ST_SOLVE_FAILED] == 0 and stf[_lib.ST_BWD_NONCONV] == 0
