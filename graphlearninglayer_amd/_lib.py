@@ -50,6 +50,7 @@ EXPORTS = (
     "gll_ce_head_scratch_bytes", "gll_ce_head_batched", "gll_graph", "gll_workspace_view",
     "gll_cg_csr_workspace_bytes", "gll_cg_csr", "gll_prof_enable", "gll_prof_read",
     "gll_kernel_name", "gll_strerror", "gll_set_knob", "gll_build_id", "gll_select_route",
+    "gll_workspace_solve_view",
 )
 
 
@@ -65,6 +66,12 @@ class View(ct.Structure):
     _fields_ = [(name, ct.c_void_p) for name in (
         "knn_idx", "knn_d2", "eps", "row_start", "row_len", "col", "w", "d2", "deg", "U32",
         "wadj", "status")]
+
+
+class SolveView(ct.Structure):
+    """gll_solve_view: what the row build writes for the Luu solves (include/gll.h)."""
+    _fields_ = [(name, ct.c_void_p) for name in ("ucnt", "diag", "rhs", "P", "ell", "vr")] + [
+        (name, ct.c_int32) for name in ("SE", "VRM", "Wcap", "RCAP")]
 
 
 _lock = threading.Lock()
@@ -96,6 +103,8 @@ def _declare(lib):
     lib.gll_graph.restype = i32
     lib.gll_workspace_view.argtypes = [P, vp, ct.POINTER(View)]
     lib.gll_workspace_view.restype = i32
+    lib.gll_workspace_solve_view.argtypes = [P, vp, ct.POINTER(SolveView)]
+    lib.gll_workspace_solve_view.restype = i32
     lib.gll_cg_csr_workspace_bytes.argtypes = [i32, i32]
     lib.gll_cg_csr_workspace_bytes.restype = sz
     lib.gll_cg_csr.argtypes = [i32, i32, vp, vp, vp, vp, vp, ct.c_float, i32, vp, vp, vp, vp]

@@ -384,6 +384,24 @@ int gll_workspace_view(const gll_problem* p, void* ws, gll_view* out) {
     return GLL_OK;
 }
 
+int gll_workspace_solve_view(const gll_problem* p, void* ws, gll_solve_view* out) {
+    int rc = check(p);
+    if (rc != GLL_OK) return rc;
+    if (!ws || !out) return GLL_ERR_INVALID_ARG;
+    Layout L(*p);
+    out->ucnt = L.at<int32_t>(ws, L.ucnt);
+    out->diag = L.at<float>(ws, L.diag);
+    out->rhs = L.at<float>(ws, L.rhs);
+    out->P = L.at<float>(ws, L.P);
+    out->ell = L.at<int32_t>(ws, L.ell);
+    out->vr = L.at<char>(ws, L.vr);
+    out->SE = ell_emit(L, 1);
+    out->VRM = L.VRM;
+    out->Wcap = L.Wcap;
+    out->RCAP = L.RCAP;
+    return GLL_OK;
+}
+
 int gll_cg_csr(int m, int C, const int32_t* row_ptr, const int32_t* col, const float* val,
                const float* b, float* x, float atol, int max_iter, int32_t* iters,
                int32_t* nonconv, void* workspace, void* stream) {

@@ -223,6 +223,36 @@ typedef struct gll_view {
 } gll_view;
 int gll_workspace_view(const gll_problem* p, void* workspace, gll_view* out);
 
+/* The arrays the row build writes for the Luu solves (m = n - base unlabeled rows, u = i - base
+ * the U index of row i), for tests of the row build alone.  Append-only beside gll_view, which
+ * stays as it is.  The solves only read them, so they stand as the row build left them after
+ * gll_forward(_batched).
+ *   ELL slice: SE slots per U row, column-major, two slots per 16-B record: slot s of row u is
+ *     the int32 pair (col - base, float bits of w) at ell[((s / 2) * m + u) * 4 + (s % 2) * 2];
+ *     the row's first SE U-block entries in column order, (0, 0.0f) past ucnt[u]; a suffix
+ *     longer than SE keeps its tail in the CSR only.  SE = 0: no slice (m > 4096).
+ *   Virtual rows: VRM slots of 48 bytes per U row (slot j of row u at vr + (u * VRM + j) * 48):
+ *     8 uint16 offsets 4 * (col - base), then 8 fp32 weights -- entries 8 j .. 8 j + 7 of the
+ *     row's U block; min(ceil(ucnt[u] / 8), VRM) slots are written, the last one padded with
+ *     (0, 0.0f), the rest of the row's slots untouched; a longer suffix keeps its tail in the
+ *     CSR only.  VRM = 0: the problem's solves do not run the balanced kernel, nothing is
+ *     written.  (VRM follows p->flags and GLL_KNOB_VR_RV as the workspace layout does.) */
+typedef struct gll_solve_view {
+    int32_t* ucnt;  /* m      entries of row base + u with col >= base: the row's sorted suffix */
+    float* diag;    /* m      deg + tau                                                      */
+    float* rhs;     /* m x C  sum over the row's labeled entries of W_ij Y_j                 */
+    float* P;       /* n x C  [Y as fp32; U32]: the labeled rows are written by the row build */
+    int32_t* ell;   /* SE x m (col, w) slots, see above                                      */
+    void* vr;       /* m x VRM 48-byte slots, see above                                      */
+    int32_t SE;     /* ELL slots per U row the row build writes: 24, 16, 4 or 0, by m        */
+    int32_t VRM;    /* virtual-row slots per U row, 0 when unused                            */
+    int32_t Wcap;   /* row slot width 5 (K - 1) + 8: a row with at most Wcap forward + reverse
+                     * entries starts at i * Wcap, longer ones in the bump region behind n Wcap */
+    int32_t RCAP;   /* reverse-list capacity per row 8 (K - 1) + 8; entries past it go through
+                     * the overflow list */
+} gll_solve_view;
+int gll_workspace_solve_view(const gll_problem* p, void* workspace, gll_solve_view* out);
+
 /* Multi-RHS Jacobi-preconditioned CG on a general SPD CSR matrix (device replacement of
  * stable_conjgrad, GLL.py:247-276, as used by utils.laplace, utils.py:589).
  * A: m x m CSR (row_ptr m+1, col, val) fp32; b, x: m x C row-major fp32 (x is output).

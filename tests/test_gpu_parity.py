@@ -91,6 +91,7 @@ def test_knn_lists_ordered_and_self_first():
 
 
 def test_graph_symmetric_sorted_and_weights():
+    from tests import rows_ref as R
     c = Case("ns_epsauto_tau0p07_f32")
     g = _gpu_knn(c.X, c.k, "auto")
     rp = g["row_ptr"].cpu().numpy()
@@ -98,15 +99,26 @@ def test_graph_symmetric_sorted_and_weights():
     w = g["w"].cpu().numpy()
     n = c.X.shape[0]
     rows = np.repeat(np.arange(n), np.diff(rp))
-    for i in range(0, n, 97):
+    for i in range(n):                                   # every row's order
         seg = col[rp[i]:rp[i + 1]]
         assert (np.diff(seg) > 0).all()
     import scipy.sparse as sp
     W = sp.csr_matrix((w, col, rp), shape=(n, n))
-    assert abs(W - W.T).max() < 1e-6
+    assert abs(W - W.T).max() == 0                       # the two directions are bitwise equal
     ind = g["knn_idx"].cpu().numpy()
-    ref = O.graph_from_knn(ind, np.sqrt(g["knn_d2"].cpu().numpy().astype(np.float64)), "auto")
+    d2k = g["knn_d2"].cpu().numpy()
+    ref = O.graph_from_knn(ind, np.sqrt(d2k.astype(np.float64)), "auto")
     assert np.array_equal(ref.rows, rows) and np.array_equal(ref.cols, col)
+    # W, d2 and deg against the float64 stage reference on the GPU's own lists and eps, under its
+    # relative elementwise bounds (tests/rows_ref.py): a weight of 1e-6 is held to ~1e-12
+    st = R.rows_stage(ind, d2k, g["eps"].cpu().numpy(), np.zeros((0, 1), np.float32), 0.0, 0, c.k,
+                      R.layout(n, 0, c.k))
+    assert np.array_equal(st.row, rows) and np.array_equal(st.col, col)
+    assert np.array_equal(g["d2"].cpu().numpy().view(np.uint32), st.d2.view(np.uint32))
+    np.testing.assert_allclose(st.W, ref.W, rtol=1e-5)   # the oracle's eps are float64 roots
+    assert (np.abs(w.astype(np.float64) - st.W) <= st.wb).all()
+    deg = g["deg"].cpu().numpy()
+    assert (np.abs(deg.astype(np.float64) - st.deg) <= st.deg_b).all()
     assert np.max(np.abs(ref.W - w)) < 1e-5
 
 
