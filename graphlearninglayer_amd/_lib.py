@@ -50,7 +50,7 @@ EXPORTS = (
     "gll_ce_head_scratch_bytes", "gll_ce_head_batched", "gll_graph", "gll_workspace_view",
     "gll_cg_csr_workspace_bytes", "gll_cg_csr", "gll_prof_enable", "gll_prof_read",
     "gll_kernel_name", "gll_strerror", "gll_set_knob", "gll_build_id", "gll_select_route",
-    "gll_workspace_solve_view",
+    "gll_workspace_solve_view", "gll_workspace_knn_view", "gll_gram_route",
 )
 
 
@@ -73,6 +73,17 @@ class SolveView(ct.Structure):
     _fields_ = [(name, ct.c_void_p) for name in ("ucnt", "diag", "rhs", "P", "ell", "vr")] + [
         (name, ct.c_int32) for name in ("SE", "VRM", "Wcap", "RCAP")]
 
+
+class KnnView(ct.Structure):
+    """gll_knn_view: what the Gram and the locality order leave in a workspace (include/gll.h)."""
+    _fields_ = [(name, ct.c_void_p) for name in (
+        "D2", "d2_scale", "xhi", "xlo", "xnrm", "pid", "perm")] + [("plane_stride", ct.c_int64)] + [
+        (name, ct.c_int32) for name in ("planes", "ldD", "rows", "d2_half", "dp", "order")]
+
+
+GRAM_ROUTE_WORDS = 9
+# gll_gram_route out[0]
+GRAM_BF3, GRAM_BF3H, GRAM_BF3S, GRAM_BF3W, GRAM_PK, GRAM_PK2 = range(6)
 
 _lock = threading.Lock()
 _lib = None
@@ -105,6 +116,10 @@ def _declare(lib):
     lib.gll_workspace_view.restype = i32
     lib.gll_workspace_solve_view.argtypes = [P, vp, ct.POINTER(SolveView)]
     lib.gll_workspace_solve_view.restype = i32
+    lib.gll_workspace_knn_view.argtypes = [P, i32, vp, ct.POINTER(KnnView)]
+    lib.gll_workspace_knn_view.restype = i32
+    lib.gll_gram_route.argtypes = [P, i32, i32, i32, ct.POINTER(ct.c_int32)]
+    lib.gll_gram_route.restype = i32
     lib.gll_cg_csr_workspace_bytes.argtypes = [i32, i32]
     lib.gll_cg_csr_workspace_bytes.restype = sz
     lib.gll_cg_csr.argtypes = [i32, i32, vp, vp, vp, vp, vp, ct.c_float, i32, vp, vp, vp, vp]

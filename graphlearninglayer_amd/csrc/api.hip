@@ -402,6 +402,47 @@ int gll_workspace_solve_view(const gll_problem* p, void* ws, gll_solve_view* out
     return GLL_OK;
 }
 
+int gll_workspace_knn_view(const gll_problem* p, int B, void* ws, gll_knn_view* out) {
+    int rc = check(p);
+    if (rc != GLL_OK) return rc;
+    if (B < 1 || B > 65535 || !ws || !out) return GLL_ERR_INVALID_ARG;
+    Layout L(*p);
+    if (L.PR < L.n && B > 1) return GLL_ERR_UNSUPPORTED;   // row panels: single graphs
+    Batch bt;
+    bt.B = B;
+    out->D2 = L.at<float>(ws, L.D2);
+    out->d2_scale = L.at<float>(ws, L.d2s);
+    out->xhi = L.at<char>(ws, L.xhi);
+    out->xlo = L.at<char>(ws, L.xlo);
+    out->xnrm = L.at<float>(ws, L.xnrm);
+    out->pid = L.at<int32_t>(ws, L.pid);
+    out->perm = L.at<int32_t>(ws, L.perm);
+    out->plane_stride = int64_t(L.n) * L.ldD;
+    out->planes = gram_planes(L, B);
+    out->ldD = L.ldD;
+    out->rows = L.PR;
+    out->d2_half = d2_half(L, bt);
+    out->dp = L.dp;
+    out->order = locality_order(L, bt);
+    return GLL_OK;
+}
+
+int gll_gram_route(const gll_problem* p, int B, int x_aligned, int cus,
+                   int32_t out[GLL_GRAM_ROUTE_WORDS]) {
+    int rc = check(p);
+    if (rc != GLL_OK) return rc;
+    if (B < 1 || B > 65535 || cus < 1 || !out) return GLL_ERR_INVALID_ARG;
+    Layout L(*p);
+    if (L.PR < L.n && B > 1) return GLL_ERR_UNSUPPORTED;   // row panels: single graphs
+    Batch bt;
+    bt.B = B;
+    const GramRoute rt = gram_route(L, bt, x_aligned && p->d % 4 == 0, cus);
+    const int32_t words[GLL_GRAM_ROUTE_WORDS] = {rt.family, rt.vec, rt.planes, rt.presplit, rt.H,
+                                                 rt.t256,   rt.tail, rt.sub,   rt.panels};
+    for (int q = 0; q < GLL_GRAM_ROUTE_WORDS; ++q) out[q] = words[q];
+    return GLL_OK;
+}
+
 int gll_cg_csr(int m, int C, const int32_t* row_ptr, const int32_t* col, const float* val,
                const float* b, float* x, float atol, int max_iter, int32_t* iters,
                int32_t* nonconv, void* workspace, void* stream) {

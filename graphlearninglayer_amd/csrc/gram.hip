@@ -327,8 +327,7 @@ __global__ __launch_bounds__(1024) void gram_bf3_kernel(const float* __restrict_
 // halves) stage 128 rows x 128 features in 70 KiB: two workgroups per CU, one round.  Lanes
 // 0..31 and 32..63 of a wave hold two rows (512 contiguous bytes each), so the loads stay
 // coalesced; the epilogue is bf3_epilogue<512>.
-constexpr int kHP = 128;          // features of the half tile
-constexpr int kHS = kHP + 8;      // its LDS plane row stride (bf16)
+constexpr int kHS = kHP + 8;      // LDS plane row stride (bf16) of the half tile (kHP features)
 template <bool VEC>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
 void gram_bf3h_kernel(const float* __restrict__ X, int n, int d, int T, float* __restrict__ D2,
@@ -1217,24 +1216,25 @@ __global__ __launch_bounds__(512) void gram_pk2_kernel(const __bf16* __restrict_
     }
 }
 
+// Every launch below follows gram_route (knn_route.h): the one place the kernels are chosen.
 hipError_t launch_gram(const Layout& L, const Batch& bt, void* ws, const float* X, bool vec,
                        hipStream_t s) {
     float* D2 = L.at<float>(ws, L.D2);
     int32_t* st = L.at<int32_t>(ws, L.status);
     int32_t* rc = L.at<int32_t>(ws, L.rev_cnt);
-    if (gram_planes(L, bt.B) == 2) {
+    const GramRoute rt = gram_route(L, bt, vec, device_cus());
+    if (rt.panels) return hipErrorInvalidValue;   // row panels: launch_gram_panel
+    prof_begin(GLL_K_GRAM, s);
+    switch (rt.family) {
+    case kGramBf3s: {
         const int T = (L.n + 63) / 64;
         const dim3 grid(T * T, bt.B);
         const size_t plane = size_t(L.n) * L.ldD;
-        prof_begin(GLL_K_GRAM, s);
-        launch_k(vec ? gram_bf3s_kernel<true> : gram_bf3s_kernel<false>, grid, 1024, 0, s, X, L.n,
-                 L.d, T, D2, L.ldD, plane, st, rc, bt.x, bt.ws);
+        launch_k(rt.vec ? gram_bf3s_kernel<true> : gram_bf3s_kernel<false>, grid, 1024, 0, s, X,
+                 L.n, L.d, T, D2, L.ldD, plane, st, rc, bt.x, bt.ws);
         prof_end(GLL_K_GRAM, s);
         return launch_status("gram.hip:launch_gram(bf3s)");
     }
-    // 128-tiles when there are enough of them to fill the chip twice (large graphs and batches;
-    // a single NS graph has only 36); 64-tiles otherwise
-    const int T = (L.n + 127) / 128;
     // pre-split GEMM from 256 tiles (NS B = 8, 288 tiles: 58 -> 45 us; a single FullySup graph,
     // 78 tiles, stays on the 64-tile kernel: 17.5 against 21.6 us).  Not for single graphs with
     // d <= 128 (utils.laplace's 250 + 60,000 points: one K stage, nothing for the DMA pipeline to
@@ -1245,42 +1245,26 @@ hipError_t launch_gram(const Layout& L, const Batch& bt, void* ws, const float* 
     // 8.7 ms at 30,250 x 512, 17.5 vs 11.4 ms at 30,250 x 1024 (tools/gram_route_probe.py,
     // profiles/r02j_gram_route.txt); the stress shape (8,192 x 1024) is the largest measured where
     // it wins, and the 12,288 cut between the two is not measured.
-    if (presplit_route(L, bt)) {
-        // split once (one pass over X), then the LDS-DMA bf16 GEMM over 128-tiles
+    case kGramPk:
+    case kGramPk2: {
+        // split once (one pass over X), then the LDS-DMA bf16 GEMM over 128- or 256-tiles
         __bf16* Ph = L.at<__bf16>(ws, L.xhi);
         __bf16* Pl = L.at<__bf16>(ws, L.xlo);
         float* nrm = L.at<float>(ws, L.xnrm);
-        const bool H = d2_half(L, bt);
-        const int T2 = (L.n + 255) / 256;
-        const bool t256 = gram_tile256(L, bt, T, T2);
-        // one 256-tile per CU at a time: a last round short of a full one (stress: 528 tiles, 16
-        // in the third round, profiles/r04b_stress_kernel_stats.csv) runs as subtiles of those
-        // tiles instead (gram_pk_kernel's D2 is bitwise the 256-tile kernel's), where they fit
-        // one round.  Round 6: 64-row subtiles (16 per tile, two workgroups per CU at 64 KiB of
-        // LDS) where they fit: stress 256 of them, one per CU, 18.8 us where 64 128-subtiles on a
-        // quarter of the chip took 31.4 (profiles/r06i_ab_gram_tail.txt); otherwise 128-subtiles
-        // (4 per tile).  More than one round of subtiles loses to a last round of 256-tiles: B =
-        // 64 NS, 128 tail tiles, 2,048 64-subtiles 58 us against ~35 for the round, and two rounds
-        // of 128-subtiles 224 -> 235 us (round 5).  GLL_KNOB_GRAM_TAIL: 1 no tail, 2 128-subtiles.
+        const bool H = rt.H;
+        const int T = (L.n + 127) / 128, T2 = (L.n + 255) / 256;
         const int64_t nt2 = int64_t(bt.B) * T2 * (T2 + 1) / 2;
-        const int cus = device_cus();
-        const int tk = knob(GLL_KNOB_GRAM_TAIL);
-        int64_t tail = t256 && nt2 > cus ? nt2 % cus : 0;
-        const int sub = (tk != 2 && tail * 16 <= 2 * int64_t(cus)) ? 16 : 4;   // subtiles per tile
-        if ((sub == 4 && tail * 4 > cus) || tk == 1) tail = 0;
-        // (Measured and dropped: the subtiles split further over 4 k-slices summed by a reduce
-        // kernel, 256 workgroups instead of 64: 250 -> 260 us, profiles/r04u_ab_tail.txt.)
-        prof_begin(GLL_K_GRAM, s);
+        const int64_t tail = rt.tail;
         prof_span(tail > 0 ? 3 : 2);
         const dim3 sgrid((L.n + 3) / 4, bt.B);
         float* d2s = L.at<float>(ws, L.d2s);
-        launch_k(vec ? gram_split_kernel<true> : gram_split_kernel<false>, sgrid, 256, 0, s, X, L.n,
-                 L.d, L.dp, Ph, Pl, nrm, st, rc, bt.x, bt.ws);
-        if (t256) {
+        launch_k(rt.vec ? gram_split_kernel<true> : gram_split_kernel<false>, sgrid, 256, 0, s, X,
+                 L.n, L.d, L.dp, Ph, Pl, nrm, st, rc, bt.x, bt.ws);
+        if (rt.t256) {
             launch_k(H ? gram_pk2_kernel<true> : gram_pk2_kernel<false>,
                      dim3(unsigned(nt2 - tail)), 512, 0, s, Ph, Pl, nrm, L.n, L.dp, T2, D2,
                      L.ldD, bt.ws, d2s);
-            if (tail > 0 && sub == 4)
+            if (tail > 0 && rt.sub == 4)
                 launch_k(H ? gram_pk_kernel<true, 128> : gram_pk_kernel<false, 128>,
                          dim3(unsigned(4 * tail)), 256, 0, s, Ph, Pl, nrm, L.n, L.dp, T, D2, L.ldD,
                          bt.ws, d2s, int(nt2 - tail));
@@ -1296,27 +1280,31 @@ hipError_t launch_gram(const Layout& L, const Batch& bt, void* ws, const float* 
         prof_end(GLL_K_GRAM, s);
         return launch_status("gram.hip:launch_gram(pk)");
     }
-    if (int64_t(bt.B) * T * (T + 1) / 2 >= 512) {
+    case kGramBf3w: {
+        const int T = (L.n + 127) / 128;
         const dim3 grid(T * (T + 1) / 2, bt.B);
-        prof_begin(GLL_K_GRAM, s);
-        launch_k(vec ? gram_bf3w_kernel<true> : gram_bf3w_kernel<false>, grid, 1024, 0, s, X, L.n,
-                 L.d, T, D2, L.ldD, st, rc, bt.x, bt.ws, 0, 0);
+        launch_k(rt.vec ? gram_bf3w_kernel<true> : gram_bf3w_kernel<false>, grid, 1024, 0, s, X,
+                 L.n, L.d, T, D2, L.ldD, st, rc, bt.x, bt.ws, 0, 0);
         prof_end(GLL_K_GRAM, s);
         return launch_status("gram.hip:launch_gram(bf3w)");
     }
-    const int T64 = (L.n + 63) / 64;
-    const dim3 grid(T64 * (T64 + 1) / 2, bt.B);
-    prof_begin(GLL_K_GRAM, s);
-    if (L.d <= kHP) {   // 1024-thread tile 17.4 -> 9.5 us at FullySup (profiles/r06v_ab_*.txt)
-        launch_k(vec ? gram_bf3h_kernel<true> : gram_bf3h_kernel<false>, grid, 512, 0, s, X, L.n,
-                 L.d, T64, D2, L.ldD, st, rc, bt.x, bt.ws);
+    case kGramBf3h: {   // 1024-thread tile 17.4 -> 9.5 us at FullySup (profiles/r06v_ab_*.txt)
+        const int T64 = (L.n + 63) / 64;
+        const dim3 grid(T64 * (T64 + 1) / 2, bt.B);
+        launch_k(rt.vec ? gram_bf3h_kernel<true> : gram_bf3h_kernel<false>, grid, 512, 0, s, X,
+                 L.n, L.d, T64, D2, L.ldD, st, rc, bt.x, bt.ws);
         prof_end(GLL_K_GRAM, s);
         return launch_status("gram.hip:launch_gram(bf3h)");
     }
-    launch_k(vec ? gram_bf3_kernel<true> : gram_bf3_kernel<false>, grid, 1024, 0, s, X, L.n, L.d,
-             T64, D2, L.ldD, st, rc, bt.x, bt.ws);
-    prof_end(GLL_K_GRAM, s);
-    return launch_status("gram.hip:launch_gram(bf3)");
+    default: {
+        const int T64 = (L.n + 63) / 64;
+        const dim3 grid(T64 * (T64 + 1) / 2, bt.B);
+        launch_k(rt.vec ? gram_bf3_kernel<true> : gram_bf3_kernel<false>, grid, 1024, 0, s, X, L.n,
+                 L.d, T64, D2, L.ldD, st, rc, bt.x, bt.ws);
+        prof_end(GLL_K_GRAM, s);
+        return launch_status("gram.hip:launch_gram(bf3)");
+    }
+    }
 }
 
 // One row panel of the Gram (build_graph's panel mode, single graphs): rows r0 .. r0 + rows - 1
@@ -1327,12 +1315,13 @@ hipError_t launch_gram_panel(const Layout& L, void* ws, const float* X, bool vec
     float* D2 = L.at<float>(ws, L.D2);
     int32_t* st = L.at<int32_t>(ws, L.status);
     int32_t* rc = L.at<int32_t>(ws, L.rev_cnt);
+    const GramRoute rt = gram_route(L, Batch{}, vec, 0);   // a panel route reads no CU count
     const int T = (L.n + 127) / 128, pt = (rows + 127) / 128;
-    if (r0 % 128 || pt <= 0) return hipErrorInvalidValue;
+    if (!rt.panels || rt.family != kGramBf3w || r0 % 128 || pt <= 0) return hipErrorInvalidValue;
     const dim3 grid(unsigned(int64_t(pt) * T));
     prof_begin(GLL_K_GRAM, s);
-    launch_k(vec ? gram_bf3w_kernel<true> : gram_bf3w_kernel<false>, grid, 1024, 0, s, X, L.n, L.d,
-             T, D2, L.ldD, st, rc, size_t(0), size_t(0), r0, pt);
+    launch_k(rt.vec ? gram_bf3w_kernel<true> : gram_bf3w_kernel<false>, grid, 1024, 0, s, X, L.n,
+             L.d, T, D2, L.ldD, st, rc, size_t(0), size_t(0), r0, pt);
     prof_end(GLL_K_GRAM, s);
     return launch_status("gram.hip:launch_gram_panel");
 }

@@ -31,11 +31,10 @@ constexpr int kPK2 = 32;   // features per k-stage of the 256-tile kernel (gram_
 // with fewer waves of one-workgroup-per-CU rounds x k-stage bytes (a round of 256-tiles moves
 // the same 64 KiB per stage as one of 128-tiles but does 4x the work, in twice the stages).
 // The knob GLL_KNOB_GRAM_TILE = 128 / 256 forces one (tests).
-inline bool gram_tile256(const Layout& L, const Batch& bt, int T, int T2) {
+inline bool gram_tile256(const Layout& L, const Batch& bt, int T, int T2, int cus) {
     if (knob(GLL_KNOB_GRAM_TILE) > 0) return knob(GLL_KNOB_GRAM_TILE) == 256 && L.dp % kPK2 == 0;
     // (d <= 128: a tile is 4 k-stages; the FullySup shape measured 225 -> 230 us at B = 64)
     if (L.dp % kPK2 || L.dp <= 128) return false;
-    const int cus = device_cus();
     const int64_t t1 = int64_t(bt.B) * T * (T + 1) / 2, t2 = int64_t(bt.B) * T2 * (T2 + 1) / 2;
     const int64_t r1 = (t1 + cus - 1) / cus, r2 = (t2 + cus - 1) / cus;
     return r2 * 2 * (L.dp / kPK2) * kPK2 < r1 * (L.dp / kPK) * kPK;   // stage bytes equal
@@ -56,6 +55,78 @@ inline bool presplit_route(const Layout& L, const Batch& bt) {
 inline bool d2_half(const Layout& L, const Batch& bt) {
     return !(L.flags & GLL_FLAG_D2_F32) && bt.B > 1 && presplit_route(L, bt) &&
            L.K - 1 <= kMaxKm1;
+}
+
+// ---------------------------------------------------------------------------------------
+// The Gram's route: which kernels of gram.hip a graph build launches.  gram_route computes it
+// from the problem and the CU count alone; launch_gram and launch_gram_panel launch from it, and
+// gll_gram_route (api.hip) reports it without a GPU, so the report cannot drift from the launch.
+// ---------------------------------------------------------------------------------------
+constexpr int kHP = 128;   // features of the half tile (gram_bf3h_kernel)
+enum GramFamily {
+    kGramBf3 = 0,    // gram_bf3_kernel<VEC>: 64-tiles, phases of 256 features
+    kGramBf3h = 1,   // gram_bf3h_kernel<VEC>: the half tile, d <= kHP
+    kGramBf3s = 2,   // gram_bf3s_kernel<VEC>: split-phase, two planes
+    kGramBf3w = 3,   // gram_bf3w_kernel<VEC>: inline-split 128-tiles (and every row panel)
+    kGramPk = 4,     // gram_split_kernel<VEC> + gram_pk_kernel<H, 128>
+    kGramPk2 = 5,    // gram_split_kernel<VEC> + gram_pk2_kernel<H> (+ a tail of gram_pk_kernel)
+};
+struct GramRoute {
+    int family;     // GramFamily
+    int vec;        // VEC of the inline-split kernel or of gram_split_kernel
+    int planes;     // D2 planes written (gram_planes)
+    int presplit;   // gram_split_kernel runs first (xhi / xlo / xnrm are written)
+    int H;          // D2 stored as fp16 x s (d2_half)
+    int t256;       // 256-tiles (gram_pk2_kernel)
+    int tail;       // 256-tiles of the last round that run as subtiles on gram_pk_kernel<H, TS>
+    int sub;        // subtiles per such tile: 16 (TS = 64) or 4 (TS = 128); 0 without a tail
+    int panels;     // row panels (launch_gram_panel once per panel); 0: the whole matrix
+};
+inline GramRoute gram_route(const Layout& L, const Batch& bt, bool vec, int cus) {
+    GramRoute r{};
+    r.vec = vec;
+    r.planes = gram_planes(L, bt.B);
+    if (L.PR < L.n) {   // row panels: rectangular tiles on the inline-split 128-tile kernel
+        r.family = kGramBf3w;
+        r.panels = (L.n + L.PR - 1) / L.PR;
+        return r;
+    }
+    if (r.planes == 2) {
+        r.family = kGramBf3s;
+        return r;
+    }
+    // 128-tiles when there are enough of them to fill the chip twice (large graphs and batches;
+    // a single NS graph has only 36); 64-tiles otherwise
+    const int T = (L.n + 127) / 128;
+    if (presplit_route(L, bt)) {
+        const int T2 = (L.n + 255) / 256;
+        r.presplit = 1;
+        r.H = d2_half(L, bt);
+        r.t256 = gram_tile256(L, bt, T, T2, cus);
+        r.family = r.t256 ? kGramPk2 : kGramPk;
+        // one 256-tile per CU at a time: a last round short of a full one (stress: 528 tiles, 16
+        // in the third round, profiles/r04b_stress_kernel_stats.csv) runs as subtiles of those
+        // tiles instead (gram_pk_kernel's D2 is bitwise the 256-tile kernel's), where they fit
+        // one round.  Round 6: 64-row subtiles (16 per tile, two workgroups per CU at 64 KiB of
+        // LDS) where they fit: stress 256 of them, one per CU, 18.8 us where 64 128-subtiles on a
+        // quarter of the chip took 31.4 (profiles/r06i_ab_gram_tail.txt); otherwise 128-subtiles
+        // (4 per tile).  More than one round of subtiles loses to a last round of 256-tiles: B =
+        // 64 NS, 128 tail tiles, 2,048 64-subtiles 58 us against ~35 for the round, and two rounds
+        // of 128-subtiles 224 -> 235 us (round 5).  GLL_KNOB_GRAM_TAIL: 1 no tail, 2 128-subtiles.
+        const int64_t nt2 = int64_t(bt.B) * T2 * (T2 + 1) / 2;
+        const int tk = knob(GLL_KNOB_GRAM_TAIL);
+        int64_t tail = r.t256 && nt2 > cus ? nt2 % cus : 0;
+        const int sub = (tk != 2 && tail * 16 <= 2 * int64_t(cus)) ? 16 : 4;   // subtiles per tile
+        if ((sub == 4 && tail * 4 > cus) || tk == 1) tail = 0;
+        // (Measured and dropped: the subtiles split further over 4 k-slices summed by a reduce
+        // kernel, 256 workgroups instead of 64: 250 -> 260 us, profiles/r04u_ab_tail.txt.)
+        r.tail = int(tail);
+        r.sub = tail > 0 ? sub : 0;
+        return r;
+    }
+    if (int64_t(bt.B) * T * (T + 1) / 2 >= 512) r.family = kGramBf3w;
+    else r.family = L.d <= kHP ? kGramBf3h : kGramBf3;   // (profiles/r06v_ab_*.txt)
+    return r;
 }
 
 // ---------------------------------------------------------------------------------------

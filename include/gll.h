@@ -253,6 +253,54 @@ typedef struct gll_solve_view {
 } gll_solve_view;
 int gll_workspace_solve_view(const gll_problem* p, void* workspace, gll_solve_view* out);
 
+/* What the first stage of the graph build -- the Gram (gram.hip) and the locality order
+ * (order.hip) -- leaves in a workspace, for tests of that stage alone.  Append-only beside the
+ * other views.  `out` describes block 0 of a launch over B graphs (planes, fp16 storage and the
+ * pre-split arrays depend on B); graph g's arrays lie g * gll_workspace_bytes(p) further on.  The
+ * select and everything after it only read these arrays, so they stand as the Gram left them.
+ *   D2: `planes` planes of `rows` x ldD elements, `plane_stride` elements apart; the select sums
+ *     the planes in order.  rows = n, or the panel height PR < n of a row-panel build, where D2
+ *     holds what the last panels left (panel r0 writes buffer rows 0 .. min(PR, n - r0) - 1).
+ *     d2_half: the elements are fp16 of D2 x *d2_scale (element (i, j) the (i * ldD + j)-th half
+ *     of the buffer), d2_scale a power of two every tile of the GEMM stores; else fp32 and
+ *     d2_scale is not written.
+ *   xhi / xlo / xnrm: the bf16 planes n x dp of a = x - x_0 (hi = bf16(a), lo = bf16(a - hi),
+ *     zero from d to dp) and |a_i|^2, written on the pre-split route only (gll_gram_route).
+ *   pid / perm: the locality order, written for single graphs with n >= 1024 and more than
+ *     4 MB of X (and no row panels, no GLL_FLAG_ROW_ORDER_OFF): pid[i] = pivot | rank << 8 with
+ *     rank the row's position among the rows of its 64-row block at that pivot, perm the rows
+ *     grouped by pivot, blocks in order within a pivot. */
+typedef struct gll_knn_view {
+    void* D2;             /* fp32, or fp16 when d2_half                                    */
+    float* d2_scale;      /* the fp16 scale word s                                         */
+    void* xhi;            /* n x dp bf16                                                   */
+    void* xlo;            /* n x dp bf16                                                   */
+    float* xnrm;          /* n                                                             */
+    int32_t* pid;         /* n                                                             */
+    int32_t* perm;        /* n                                                             */
+    int64_t plane_stride; /* elements between D2 planes                                    */
+    int32_t planes;       /* planes the Gram writes: 1 or 2                                */
+    int32_t ldD;          /* leading dimension of a D2 plane (n rounded up to 4)           */
+    int32_t rows;         /* rows of the D2 buffer (PR)                                    */
+    int32_t d2_half;      /* 1: D2 holds fp16 x s                                          */
+    int32_t dp;           /* d rounded up to 64                                            */
+    int32_t order;        /* 1: the build writes pid / perm                                */
+} gll_knn_view;
+int gll_workspace_knn_view(const gll_problem* p, int B, void* workspace, gll_knn_view* out);
+
+/* Diagnostic: the kernels of gram.hip a graph build over B graphs launches on a device with
+ * `cus` compute units, x_aligned saying whether X is 16-B aligned.  No HIP call: it runs without
+ * a GPU, and the launchers launch from the same record.  out[0] = kernel family (0 gram_bf3,
+ * 1 gram_bf3h, 2 gram_bf3s, 3 gram_bf3w, 4 gram_split + gram_pk<H, 128>, 5 gram_split +
+ * gram_pk2<H>), out[1] = VEC of the inline-split kernel or of gram_split, out[2] = D2 planes,
+ * out[3] = 1 on the pre-split route, out[4] = H (fp16 D2), out[5] = 1 for 256-tiles, out[6] =
+ * 256-tiles of the last round that run as subtiles on gram_pk<H, TS>, out[7] = subtiles per such
+ * tile (16: TS = 64, 4: TS = 128, 0: no tail), out[8] = row panels (0: the whole matrix in one
+ * launch).  Reads GLL_KNOB_GRAM_TILE and GLL_KNOB_GRAM_TAIL. */
+#define GLL_GRAM_ROUTE_WORDS 9
+int gll_gram_route(const gll_problem* p, int B, int x_aligned, int cus,
+                   int32_t out[GLL_GRAM_ROUTE_WORDS]);
+
 /* Multi-RHS Jacobi-preconditioned CG on a general SPD CSR matrix (device replacement of
  * stable_conjgrad, GLL.py:247-276, as used by utils.laplace, utils.py:589).
  * A: m x m CSR (row_ptr m+1, col, val) fp32; b, x: m x C row-major fp32 (x is output).
