@@ -26,7 +26,13 @@ Deliberate differences from the reference (all documented in DESIGN.md):
     (the reference returns None for them, GLL.py:177): tau / epsilon may be one-element
     tensors, whose value is read once in the forward (a host sync when on the GPU), and their
     gradients come from one extra pass over the graph (gll_param_grad_batched, DESIGN.md
-    §3.6); epsilon='auto' has no epsilon input and so no epsilon gradient.
+    §3.6); epsilon='auto' has no epsilon input and so no epsilon gradient;
+  * an optional last argument `normalize` (bool, False by default) of apply / ce_loss scales
+    the rows of X to unit length inside the layer -- what every network of the reference does
+    with F.normalize(feat, dim=1) in its last line (networks/BuildNet.py:101) -- and float16 /
+    bfloat16 features are read as they are: one launch in front of the graph build, one behind
+    its backward, the gradient in X's dtype (gll_features_forward / _backward, DESIGN.md §3.8;
+    unit_features / unit_features_backward are the two stages on their own).
 """
 from __future__ import annotations
 
@@ -187,7 +193,8 @@ def _stream(dev) -> int:
 class LaplaceLearningSparseHard(torch.autograd.Function):
     """Graph Laplace learning layer; labeled rows of X come first (GLL.py:11).
 
-    `LaplaceLearningSparseHard.apply(X, label_matrix, tau=0, epsilon='auto'[, k=25])` is the
+    `LaplaceLearningSparseHard.apply(X, label_matrix, tau=0, epsilon='auto'[, k=25[,
+    normalize=False]])` is the
     native function of _gll_torch.so (csrc/torch_ext.cpp): argument checks, the forward
     kernels and one autograd node whose backward runs the backward kernels -- the whole host
     side of a call in C++.  `apply_python` is the same call as a Python
@@ -361,6 +368,79 @@ class _CeLossPython(torch.autograd.Function):
         need = ctx.needs_input_grad
         gX, gY, gtau, geps = _layer_backward(ctx, g, (need[0], need[1], need[3], need[4]))
         return gX, gY, None, gtau, geps, None, None
+
+
+# ----------------------------------------------------------------------------------------
+# The front end on its own (gll_features_forward / gll_features_backward): what
+# apply / ce_loss run in front of the graph build for normalize=True or fp16 / bf16 features
+# ----------------------------------------------------------------------------------------
+_XT_CODES = {torch.float32: _lib.XT_F32, torch.float16: _lib.XT_F16, torch.bfloat16: _lib.XT_BF16}
+
+
+def _xt_code(dtype):
+    try:
+        return _XT_CODES[dtype]
+    except KeyError:
+        raise TypeError(f"features must be float32, float16 or bfloat16, got {dtype}") from None
+
+
+def _rows_of(t: torch.Tensor, what: str):
+    if t.dim() not in (2, 3):
+        raise ValueError(f"{what} must be n x d or B x n x d")
+    d = t.shape[-1]
+    if not 1 <= d <= _lib.MAX_D_FEATURES:
+        raise ValueError(f"d = {d}: the front end holds rows of 1 <= d <= {_lib.MAX_D_FEATURES}")
+    return t.numel() // d, d
+
+
+def unit_features(Z: torch.Tensor, normalize: bool = True):
+    """X^, rnorm = unit_features(Z): the fp32 rows the layer builds its graph on, from Z
+    (n x d or B x n x d; float32, float16 or bfloat16) in one launch on the current stream.
+    normalize=True: X^ = F.normalize(Z.float(), dim=-1) and rnorm = 1 / max(|z_i|, 1e-12) per
+    row (Z's shape without the last dimension); False: X^ = Z.float() and rnorm is None.  For
+    callers who cache features; apply(X^, ...) is bitwise apply(Z, ..., normalize=True)."""
+    if not isinstance(normalize, bool):
+        raise TypeError("normalize must be a bool")
+    code = _xt_code(Z.dtype)
+    rows, d = _rows_of(Z, "Z")
+    dev = _device_for(Z)
+    with torch.cuda.device(dev):
+        Zd = Z.detach().to(dev).contiguous()
+        X = torch.empty(Z.shape, dtype=torch.float32, device=dev)
+        rnorm = torch.empty(Z.shape[:-1], dtype=torch.float32, device=dev) if normalize else None
+        _lib.check(_lib.lib().gll_features_forward(
+            rows, d, Zd.data_ptr(), code, _lib.UF_NORMALIZE if normalize else 0, X.data_ptr(),
+            None if rnorm is None else rnorm.data_ptr(), _stream(dev)), "gll_features_forward")
+    return X, rnorm
+
+
+def unit_features_backward(gX: torch.Tensor, X: torch.Tensor, rnorm, dtype,
+                           normalize: bool = True):
+    """gZ = unit_features_backward(gX, X^, rnorm, dtype): the gradient with respect to the Z
+    that unit_features turned into (X^, rnorm), from gX = dloss/dX^ (fp32, X^'s shape), rounded
+    once to `dtype` (Z's: float32, float16 or bfloat16); one launch on the current stream.
+    normalize=False: gZ = gX.to(dtype), X^ and rnorm are not read and may be None."""
+    if not isinstance(normalize, bool):
+        raise TypeError("normalize must be a bool")
+    code = _xt_code(dtype)
+    rows, d = _rows_of(gX, "gX")
+    dev = _device_for(gX)
+
+    def f32(t, shape, what):
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{what} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+        return t.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+    with torch.cuda.device(dev):
+        g = f32(gX, gX.shape, "gX")
+        Xd = f32(X, gX.shape, "X") if normalize else None
+        rn = f32(rnorm, gX.shape[:-1], "rnorm") if normalize else None
+        gZ = torch.empty(gX.shape, dtype=dtype, device=dev)
+        _lib.check(_lib.lib().gll_features_backward(
+            rows, d, g.data_ptr(), None if Xd is None else Xd.data_ptr(),
+            None if rn is None else rn.data_ptr(), _lib.UF_NORMALIZE if normalize else 0,
+            gZ.data_ptr(), code, _stream(dev)), "gll_features_backward")
+    return gZ
 
 
 def custom_ce_loss(pred, targets):

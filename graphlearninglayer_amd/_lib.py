@@ -42,6 +42,9 @@ K_PARAM = 7   # param_grad_kernel: label_matrix / tau / eps gradients
 K_LOSS = 8    # ce_head_kernel: cross-entropy head (gll_ce_head_batched)
 K_COUNT = 9
 PG_Y, PG_TAU, PG_EPS = 1, 2, 4   # gll_param_grad_batched `what` bits
+XT_F32, XT_F16, XT_BF16 = 0, 1, 2   # gll_features_* element types of Z / gZ
+UF_NORMALIZE = 1                 # gll_features_* flag: unit-norm rows
+MAX_D_FEATURES = 4096            # gll_features_*: 1 <= d <= 4096 (one wave holds a row)
 
 # every symbol include/gll.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -51,6 +54,7 @@ EXPORTS = (
     "gll_cg_csr_workspace_bytes", "gll_cg_csr", "gll_prof_enable", "gll_prof_read",
     "gll_kernel_name", "gll_strerror", "gll_set_knob", "gll_build_id", "gll_select_route",
     "gll_workspace_solve_view", "gll_workspace_knn_view", "gll_gram_route",
+    "gll_features_forward", "gll_features_backward", "gll_features_calls",
 )
 
 
@@ -138,6 +142,12 @@ def _declare(lib):
     lib.gll_strerror.restype = ct.c_char_p
     lib.gll_build_id.argtypes = []
     lib.gll_build_id.restype = ct.c_char_p
+    lib.gll_features_forward.argtypes = [ct.c_int64, ct.c_int32, vp, i32, i32, vp, vp, vp]
+    lib.gll_features_forward.restype = i32
+    lib.gll_features_backward.argtypes = [ct.c_int64, ct.c_int32, vp, vp, vp, i32, vp, i32, vp]
+    lib.gll_features_backward.restype = i32
+    lib.gll_features_calls.argtypes = []
+    lib.gll_features_calls.restype = ct.c_int64
     return lib
 
 

@@ -1,7 +1,7 @@
 // api.hip -- the extern "C" boundary declared in include/gll.h.
 //
 // Orchestrates the kernels of gram.hip, select.hip, order.hip, rows.hip, solve.hip / gridcg.hip,
-// grad.hip, param_grad.hip and loss.hip on the caller's stream.  No allocation, no host synchronisation: the caller owns the workspace (the
+// grad.hip, param_grad.hip, loss.hip and features.hip on the caller's stream.  No allocation, no host synchronisation: the caller owns the workspace (the
 // Python mirror takes it from torch's caching allocator) and keeps it alive from
 // gll_forward to gll_backward, as the reference keeps its graph on ctx (GLL.py:69-70).
 #include <atomic>
@@ -363,6 +363,36 @@ int gll_ce_head_batched(const gll_problem* p, int B, void* ws, const int64_t* ta
     return hip_status(launch_ce_head(L, B, ws, targets, loss, gbar, row_loss, pred_label, correct,
                                      scratch, static_cast<hipStream_t>(stream)));
 }
+
+static int check_features(int64_t rows, int32_t d, int z_dtype, int flags) {
+    if (rows < 0 || d < 1 || d > 4096) return GLL_ERR_INVALID_ARG;
+    if (z_dtype != GLL_XT_F32 && z_dtype != GLL_XT_F16 && z_dtype != GLL_XT_BF16)
+        return GLL_ERR_INVALID_ARG;
+    if (flags & ~GLL_UF_NORMALIZE) return GLL_ERR_INVALID_ARG;
+    return GLL_OK;
+}
+
+int gll_features_forward(int64_t rows, int32_t d, const void* Z, int z_dtype, int flags, float* X,
+                         float* rnorm, void* stream) {
+    const int rc = check_features(rows, d, z_dtype, flags);
+    if (rc != GLL_OK) return rc;
+    if (rows == 0) return GLL_OK;
+    if (!Z || !X || ((flags & GLL_UF_NORMALIZE) && !rnorm)) return GLL_ERR_INVALID_ARG;
+    return hip_status(launch_unit_rows(rows, d, Z, z_dtype, flags, X, rnorm,
+                                       static_cast<hipStream_t>(stream)));
+}
+
+int gll_features_backward(int64_t rows, int32_t d, const float* gX, const float* X,
+                          const float* rnorm, int flags, void* gZ, int z_dtype, void* stream) {
+    const int rc = check_features(rows, d, z_dtype, flags);
+    if (rc != GLL_OK) return rc;
+    if (rows == 0) return GLL_OK;
+    if (!gX || !gZ || ((flags & GLL_UF_NORMALIZE) && (!X || !rnorm))) return GLL_ERR_INVALID_ARG;
+    return hip_status(launch_unit_grad(rows, d, gX, X, rnorm, flags, gZ, z_dtype,
+                                       static_cast<hipStream_t>(stream)));
+}
+
+int64_t gll_features_calls(void) { return features_calls(); }
 
 int gll_workspace_view(const gll_problem* p, void* ws, gll_view* out) {
     int rc = check(p);

@@ -658,5 +658,12 @@ size_t ce_head_scratch_bytes(int m, int B);
 hipError_t launch_ce_head(const Layout& L, int B, void* ws, const int64_t* targets, double* loss,
                           float* gbar, double* row_loss, int64_t* pred_label, int64_t* correct,
                           void* scratch, hipStream_t s);
+// The layer's front end (features.hip): rows of fp32 / fp16 / bf16 features into fp32 rows,
+// optionally unit-norm, and the gradient's way back.  features_calls: launches so far.
+hipError_t launch_unit_rows(int64_t rows, int d, const void* Z, int z_dtype, int flags, float* X,
+                            float* rnorm, hipStream_t s);
+hipError_t launch_unit_grad(int64_t rows, int d, const float* gX, const float* X,
+                            const float* rnorm, int flags, void* gZ, int z_dtype, hipStream_t s);
+int64_t features_calls();
 
 }  // namespace gll

@@ -3,7 +3,8 @@
 // The reference's LaplaceLearningSparseHard is a Python torch.autograd.Function
 // (/root/reference/GLL.py:10-177).  At ~10^4 calls/s the host side of a call is on the step's
 // critical path, so everything `apply` does before and after its kernels lives here:
-//   * `apply(X, label_matrix, tau=0, epsilon='auto', k=25)` is a METH_FASTCALL CPython function
+//   * `apply(X, label_matrix, tau=0, epsilon='auto', k=25, normalize=False)` is a METH_FASTCALL
+//     CPython function
 //     (no pybind dispatch, no Python frame): argument checks with the reference's error
 //     behaviour, tensor marshalling, the workspace from torch's caching allocator, gll_forward on
 //     the current HIP stream, and -- when X, label_matrix or a tensor tau / epsilon requires
@@ -11,10 +12,15 @@
 //     torch::autograd::Function bookkeeping).  The node's backward is gll_backward_batched, plus
 //     one gll_param_grad_batched call when a gradient of label_matrix, tau or epsilon is wanted
 //     (the reference returns None for them, GLL.py:177);
-//   * `ce_loss(X, label_matrix, targets, tau=0, epsilon='auto', k=25)` is the same call followed
+//   * `ce_loss(X, label_matrix, targets, tau=0, epsilon='auto', k=25, normalize=False)` is the
+//     same call followed
 //     by the cross-entropy head (gll_ce_head_batched: custom_ce_loss of losses.py:128-136 and the
 //     argmax accuracy of FullySup.py:156-171 in one kernel); its node is the same one, holding
 //     the head's dloss/dU;
+//   * the front end: an fp32 X with normalize=False goes to the kernels as it is;
+//     normalize=True, or an fp16 / bf16 X, takes one gll_features_forward launch into a fresh fp32
+//     X^ (and rnorm), which the node saves instead of X, and one gll_features_backward launch that
+//     writes the gradient in X's dtype;
 //   * the device status words (tiny eps, CG non-convergence, grid-barrier failure) accumulate in
 //     a sticky per-device sink that is copied to pinned memory every kFlushEvery calls and turned
 //     into the reference's warnings (GLL.py:240-241, 273-274) at a later call, with no host sync.
@@ -213,6 +219,16 @@ at::Tensor features(const at::Tensor& X, const c10::Device& dev) {
     return X32;
 }
 
+// Element type of the front end (gll_features_*) for a feature dtype; < 0: none (torch casts)
+int feature_code(at::ScalarType t) {
+    switch (t) {
+        case at::kFloat: return GLL_XT_F32;
+        case at::kHalf: return GLL_XT_F16;
+        case at::kBFloat16: return GLL_XT_BF16;
+        default: return -1;
+    }
+}
+
 void check_rc(int rc, const char* what) {
     TORCH_CHECK(rc == GLL_OK, what, " failed: ", gll_strerror(rc), " (code ", rc, ")");
 }
@@ -258,7 +274,11 @@ struct GradLike {
 };
 
 struct LaplaceBackward : public torch::autograd::Node {
-    torch::autograd::SavedVariable X_;
+    torch::autograd::SavedVariable X_;   // X, or on the front-end route the fp32 X^ made from it
+    GradLike Xin_;                       // X as given: its gradient's dtype, device and shape
+    bool front_ = false;                 // gll_features_forward made X^ (and rnorm_)
+    int zcode_ = GLL_XT_F32, uflags_ = 0;
+    at::Tensor rnorm_;
     at::Tensor ws_;
     gll_problem p_{};
     int64_t B_ = 1;
@@ -274,6 +294,7 @@ struct LaplaceBackward : public torch::autograd::Node {
     void release_variables() override {
         std::lock_guard<std::mutex> lk(mutex_);
         X_.reset_data();
+        rnorm_.reset();
         ws_.reset();
         gbar_.reset();
     }
@@ -285,7 +306,7 @@ struct LaplaceBackward : public torch::autograd::Node {
         if (!grads[0].defined()) return out;
         const c10::Device dev = ws_.device();
         c10::DeviceGuard guard(dev);
-        at::Tensor X32 = features(X, dev);
+        at::Tensor X32 = front_ ? X : features(X, dev);
         at::Tensor g = grads[0].device() == dev ? grads[0] : grads[0].to(dev);
         if (gbar_.defined()) {   // ce_loss: dL/dU = gbar * dL/dloss, broadcast over the graphs
             const at::Tensor gl = gbar_.dim() == 3 ? g.reshape({-1, 1, 1}) : g.reshape({});
@@ -309,8 +330,20 @@ struct LaplaceBackward : public torch::autograd::Node {
             what |= GLL_PG_EPS;
         if (what) param_grads(what, X32, out);
         if (task_should_compute_output(0)) {
-            if (gradX.device() != X.device() || gradX.scalar_type() != X.scalar_type())
-                gradX = gradX.to(X.device(), X.scalar_type());
+            if (front_) {   // through the normalisation, rounded once to the front end's dtype
+                const at::ScalarType zt = zcode_ == GLL_XT_F16    ? at::kHalf
+                                          : zcode_ == GLL_XT_BF16 ? at::kBFloat16
+                                                                  : at::kFloat;
+                at::Tensor gZ = at::empty(X.sizes(), X32.options().dtype(zt));
+                check_rc(gll_features_backward(
+                             B_ * int64_t(p_.n), p_.d, gradX.data_ptr<float>(), X32.data_ptr<float>(),
+                             rnorm_.defined() ? rnorm_.data_ptr<float>() : nullptr, uflags_,
+                             gZ.data_ptr(), zcode_, current_stream(dev.index())),
+                         "gll_features_backward");
+                gradX = gZ;
+            }
+            if (gradX.device() != Xin_.device || gradX.scalar_type() != Xin_.dtype)
+                gradX = gradX.to(Xin_.device, Xin_.dtype);
             out[0] = gradX;
         }
         return out;
@@ -361,7 +394,7 @@ struct LaplaceBackward : public torch::autograd::Node {
 };
 
 // ------------------------------------------------------------------------------------------
-// apply(X, label_matrix, tau=0, epsilon='auto', k=25)        GLL.py:14-73
+// apply(X, label_matrix, tau=0, epsilon='auto', k=25, normalize=False)        GLL.py:14-73
 // ------------------------------------------------------------------------------------------
 double parse_float(PyObject* o, const char* what) {
     const double v = PyFloat_AsDouble(o);
@@ -443,6 +476,9 @@ void collect_args(const char* fn, const char* const* names, int nn, PyObject* co
 struct LayerCall {
     at::Tensor X, Y, tau_t, eps_t;   // the inputs as given (tau_t / eps_t: defined where tensors)
     at::Tensor X32, ws, U;
+    at::Tensor rnorm;                // front-end route with normalize: 1 / max(|z_i|, 1e-12)
+    bool front = false;              // X32 is the X^ gll_features_forward made
+    int zcode = GLL_XT_F32, uflags = 0;
     gll_problem p{};
     int64_t B = 1, n = 0, base = 0, C = 0;
     bool batched = false;
@@ -452,7 +488,7 @@ struct LayerCall {
 };
 
 void layer_forward(LayerCall& c, const char* fn, PyObject* aX, PyObject* aY, PyObject* atau,
-                   PyObject* aeps, PyObject* ak) {
+                   PyObject* aeps, PyObject* ak, PyObject* anorm) {
     if (!aX || !aY) raise_py(PyExc_TypeError, std::string(fn) + "() needs X and label_matrix");
     c.X = tensor_arg(aX, "X");
     c.Y = tensor_arg(aY, "label_matrix");
@@ -468,6 +504,11 @@ void layer_forward(LayerCall& c, const char* fn, PyObject* aX, PyObject* aY, PyO
             PyErr_Clear();
             raise_py(PyExc_TypeError, "k must be an int");
         }
+    }
+    bool normalize = false;
+    if (anorm) {
+        if (!PyBool_Check(anorm)) raise_py(PyExc_TypeError, "normalize must be a bool");
+        normalize = anorm == Py_True;
     }
     if ((X.dim() != 2 && X.dim() != 3) || (Y.dim() != 2 && Y.dim() != X.dim()))
         raise_py(PyExc_ValueError,
@@ -493,7 +534,28 @@ void layer_forward(LayerCall& c, const char* fn, PyObject* aX, PyObject* aY, PyO
     if (!st.order.empty()) poll(st, false);
     const bool batched = X.dim() == 3;
     const int64_t B = batched ? X.size(0) : 1;
-    c.X32 = features(X, dev);
+    c.s = current_stream(devi);
+    const bool half = X.scalar_type() == at::kHalf || X.scalar_type() == at::kBFloat16;
+    if (normalize || half) {
+        // the front end: one launch over all B n rows converts (and normalises) into a fresh X^
+        if (d > 4096)
+            raise_py(PyExc_ValueError, "normalize=True and fp16 / bf16 features need d <= 4096, got d = " +
+                                           std::to_string(d));
+        at::Tensor Z = X.detach();
+        if (feature_code(Z.scalar_type()) < 0) Z = Z.to(at::kFloat);   // float64: fp32 as today
+        Z = Z.to(dev).contiguous();
+        c.front = true;
+        c.zcode = feature_code(Z.scalar_type());
+        c.uflags = normalize ? GLL_UF_NORMALIZE : 0;
+        c.X32 = at::empty(X.sizes(), Z.options().dtype(at::kFloat));
+        if (normalize) c.rnorm = at::empty({B * n}, c.X32.options());
+        check_rc(gll_features_forward(B * n, int32_t(d), Z.data_ptr(), c.zcode, c.uflags,
+                                      c.X32.data_ptr<float>(),
+                                      normalize ? c.rnorm.data_ptr<float>() : nullptr, c.s),
+                 "gll_features_forward");
+    } else {
+        c.X32 = features(X, dev);
+    }
     at::Tensor Yd = Y.device() == dev ? Y : Y.detach().to(dev);
     const int ycode = dtype_code(Yd);
     if (batched && Y.dim() == 2) Yd = Yd.unsqueeze(0).expand({B, base, C});   // shared labels
@@ -511,7 +573,6 @@ void layer_forward(LayerCall& c, const char* fn, PyObject* aX, PyObject* aY, PyO
     c.ws = at::empty({int64_t(nb) * B}, opts.dtype(at::kByte));
     c.U = batched ? at::empty({B, n - base, C}, opts.dtype(at::kDouble))
                   : at::empty({n - base, C}, opts.dtype(at::kDouble));
-    c.s = current_stream(devi);
     check_rc(gll_forward_batched(&c.p, int(B), c.X32.data_ptr<float>(), Yd.data_ptr(), ycode,
                                  c.ws.data_ptr(), c.U.data_ptr<double>(), c.s),
              "gll_forward");
@@ -541,7 +602,12 @@ std::shared_ptr<LaplaceBackward> make_node(LayerCall& c, const std::vector<at::T
     node->Y_shared_ = c.batched && c.Y.dim() == 2;
     if (c.tau_t.defined()) node->tau_.set(2, c.tau_t);
     if (c.eps_t.defined()) node->eps_.set(c.tau_t.defined() ? 3 : 2, c.eps_t);
-    node->X_ = torch::autograd::SavedVariable(c.X, false);
+    node->X_ = torch::autograd::SavedVariable(c.front ? c.X32 : c.X, false);
+    node->Xin_.set(0, c.X);
+    node->front_ = c.front;
+    node->zcode_ = c.zcode;
+    node->uflags_ = c.uflags;
+    node->rnorm_ = c.rnorm;
     node->ws_ = std::move(c.ws);
     node->p_ = c.p;
     node->B_ = c.B;
@@ -550,11 +616,11 @@ std::shared_ptr<LaplaceBackward> make_node(LayerCall& c, const std::vector<at::T
 }
 
 PyObject* apply_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames) {
-    static const char* names[] = {"X", "label_matrix", "tau", "epsilon", "k"};
-    PyObject* a[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    collect_args("apply", names, 5, args, nargs, kwnames, a);
+    static const char* names[] = {"X", "label_matrix", "tau", "epsilon", "k", "normalize"};
+    PyObject* a[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    collect_args("apply", names, 6, args, nargs, kwnames, a);
     LayerCall c;
-    layer_forward(c, "apply", a[0], a[1], a[2], a[3], a[4]);
+    layer_forward(c, "apply", a[0], a[1], a[2], a[3], a[4], a[5]);
     const std::vector<at::Tensor> inputs = grad_inputs(c);
     if (torch::autograd::compute_requires_grad(inputs))
         torch::autograd::set_history(c.U, make_node(c, inputs));
@@ -562,22 +628,22 @@ PyObject* apply_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames)
 }
 
 // ------------------------------------------------------------------------------------------
-// ce_loss(X, label_matrix, targets, tau=0, epsilon='auto', k=25): the layer and the
+// ce_loss(X, label_matrix, targets, tau=0, epsilon='auto', k=25, normalize=False): the layer and the
 // cross-entropy head its callers put behind it (losses.py:128-136, FullySup.py:156-171) in one
 // call.  gll_ce_head_batched reads the predictions the forward left in the workspace and writes
 // loss, row losses, predicted labels, the correct count and -- when a gradient is wanted --
 // dloss/dU, which the node keeps: its backward is the layer's, fed gbar * grad_loss.
 // ------------------------------------------------------------------------------------------
 PyObject* ce_loss_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames) {
-    static const char* names[] = {"X", "label_matrix", "targets", "tau", "epsilon", "k"};
-    PyObject* a[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    collect_args("ce_loss", names, 6, args, nargs, kwnames, a);
+    static const char* names[] = {"X", "label_matrix", "targets", "tau", "epsilon", "k", "normalize"};
+    PyObject* a[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    collect_args("ce_loss", names, 7, args, nargs, kwnames, a);
     if (!a[2]) raise_py(PyExc_TypeError, "ce_loss() needs targets");
     const at::Tensor& T = tensor_arg(a[2], "targets");
     if (!at::isIntegralType(T.scalar_type(), false))
         raise_py(PyExc_TypeError, "targets must hold integers");
     LayerCall c;
-    layer_forward(c, "ce_loss", a[0], a[1], a[3], a[4], a[5]);
+    layer_forward(c, "ce_loss", a[0], a[1], a[3], a[4], a[5], a[6]);
     const int64_t m = c.n - c.base;
     const bool shape_ok = c.batched ? (T.dim() == 2 && T.size(0) == c.B && T.size(1) == m)
                                     : (T.dim() == 1 && T.size(0) == m);
@@ -637,8 +703,10 @@ PyObject* entry_py(PyObject*, PyObject* const* args, Py_ssize_t nargs, PyObject*
 PyMethodDef kApplyDef = {
     "apply", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(entry_py<apply_impl>)),
     METH_FASTCALL | METH_KEYWORDS,
-    "U = LaplaceLearningSparseHard.apply(X, label_matrix, tau=0, epsilon='auto', k=25)\n"
-    "(GLL.py:14; k: neighbours incl. self, the reference hard-codes 25).  X, a floating-point\n"
+    "U = LaplaceLearningSparseHard.apply(X, label_matrix, tau=0, epsilon='auto', k=25,\n"
+    "                                    normalize=False)\n"
+    "(GLL.py:14; k: neighbours incl. self, the reference hard-codes 25; normalize=True: the rows\n"
+    "of X are scaled to unit length first, as F.normalize(X, dim=1) does).  X, a floating-point\n"
     "label_matrix and tau / a fixed epsilon given as one-element tensors are differentiable\n"
     "(a tensor's value is read once in the forward: a host sync when it lives on the GPU)"};
 
@@ -646,7 +714,8 @@ PyMethodDef kCeLossDef = {
     "ce_loss", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(entry_py<ce_loss_impl>)),
     METH_FASTCALL | METH_KEYWORDS,
     "loss, pred, pred_labels, row_loss, correct =\n"
-    "    LaplaceLearningSparseHard.ce_loss(X, label_matrix, targets, tau=0, epsilon='auto', k=25)\n"
+    "    LaplaceLearningSparseHard.ce_loss(X, label_matrix, targets, tau=0, epsilon='auto', k=25,\n"
+    "                                      normalize=False)\n"
     "apply followed by custom_ce_loss (losses.py:128-136) and the argmax accuracy\n"
     "(FullySup.py:156-171) with one extra kernel.  Only loss is differentiable (with respect to\n"
     "the inputs apply differentiates); a target outside [0, C) leaves its row out"};

@@ -5,7 +5,9 @@
  * of jwcalder/GraphLearningLayer.  Each entry point names the reference interface it
  * replaces (file:line in the reference snapshot).  Plain pointers and sizes only: device
  * pointers are HIP device memory, `stream` is a hipStream_t passed as void*.  Row-major,
- * fp32 features, int32 indices.  Inputs and outputs are caller-owned; the caller also owns
+ * int32 indices.  The graph entry points read fp32 features; gll_features_forward makes them
+ * from fp32, fp16 or bf16 rows (optionally unit-norm) and gll_features_backward takes the
+ * gradient back.  Inputs and outputs are caller-owned; the caller also owns
  * one workspace block per call (size from gll_workspace_bytes) that carries the graph from
  * gll_forward to gll_backward (the reference keeps the same state on `ctx`,
  * GLL.py:69-70).  Nothing here synchronises the host; nothing allocates; every call is
@@ -360,6 +362,39 @@ const char* gll_build_id(void);
 
 /* Human-readable message for a return code. */
 const char* gll_strerror(int code);
+
+/* The layer's front end.  Every network of the reference ends in F.normalize(feat, dim=1)
+ * (networks/BuildNet.py:101, preact_resnet.py:101, customCNN.py:36,
+ * train_and_adversarial.py:420) and GLL.py:24 leaves that to the caller; under AMP the features
+ * arrive as fp16 / bf16.  gll_features_forward turns `rows` feature rows Z (rows x d of z_dtype,
+ * row-major, contiguous) into the fp32 rows X that gll_forward(_batched) reads, in one launch.
+ * With a_k = float(z_k) (exact):
+ *   flags 0:           X[i,k] = a_k; rnorm is not touched and may be NULL
+ *   GLL_UF_NORMALIZE:  s = sum_k a_k^2 (fp32), r = 1 / max(sqrtf(s), 1e-12f) (F.normalize's
+ *                      clamp; no rescaling against overflow of s, as torch has none),
+ *                      X[i,k] = a_k r, rnorm[i] = r
+ * gll_features_backward is its backward, one launch: from fp32 gX (the gradient gll_backward wrote
+ * for X), X and rnorm as the forward left them,
+ *   GLL_UF_NORMALIZE:  t = sum_k X[i,k] gX[i,k] (fp32), out_k = r (gX[i,k] - X[i,k] t); a clamped
+ *                      row (rnorm[i] >= 1e12f) takes out_k = r gX[i,k], as the backward of torch's
+ *                      clamp_min does
+ *   flags 0:           out_k = gX[i,k]; X and rnorm may be NULL
+ * and gZ[i,k] = out_k rounded once to z_dtype (to nearest even; an fp16 overflow gives inf).
+ * One wave per row, 1 <= d <= 4096; 16-B vector accesses where d is a multiple of 16 B /
+ * sizeof(element) and the arrays are 16-B aligned, scalar ones of the same elements otherwise.
+ * The sums run in a fixed order that depends on d and z_dtype alone: no atomics, and a row's result
+ * does not depend on rows, on its place in the call or on the alignment.  rows == 0 returns GLL_OK
+ * and launches nothing; more rows than one grid holds take several launches.  Argument checks
+ * come before any HIP call. */
+#define GLL_XT_F32 0
+#define GLL_XT_F16 1
+#define GLL_XT_BF16 2
+#define GLL_UF_NORMALIZE 1
+int gll_features_forward(int64_t rows, int32_t d, const void* Z, int z_dtype, int flags,
+                         float* X, float* rnorm, void* stream);
+int gll_features_backward(int64_t rows, int32_t d, const float* gX, const float* X,
+                          const float* rnorm, int flags, void* gZ, int z_dtype, void* stream);
+int64_t gll_features_calls(void);  /* launches of either kernel so far in this process (host counter) */
 
 #ifdef __cplusplus
 }
