@@ -22,6 +22,9 @@ Deliberate differences from the reference (all documented in DESIGN.md):
   * LaplaceLearningSparseHard.ce_loss(X, label_matrix, targets, ...) is apply followed by the
     callers' custom_ce_loss (losses.py:128-136) and argmax accuracy (FullySup.py:156-171) with
     one extra kernel (gll_ce_head_batched, DESIGN.md §3.7);
+  * LaplaceLearningSparseHard.margin_loss(X, label_matrix, other, ...) is apply followed by the
+    Carlini-Wagner attack's top-2 labels and clamped margin (adversarial.py:688-751) with one
+    extra kernel (gll_margin_head_batched, DESIGN.md §3.9);
   * label_matrix (floating point), tau and a fixed epsilon are differentiable as well as X
     (the reference returns None for them, GLL.py:177): tau / epsilon may be one-element
     tensors, whose value is read once in the forward (a host sync when on the GPU), and their
@@ -219,6 +222,16 @@ class LaplaceLearningSparseHard(torch.autograd.Function):
             torch.is_tensor(t) and t.requires_grad for t in (X, label_matrix, tau, epsilon))
         return _CeLossPython.apply(X, label_matrix, targets, tau, epsilon, k, need)
 
+    margin_loss = staticmethod(_ext_mod.margin_loss)
+
+    @classmethod
+    def margin_loss_python(cls, X, label_matrix, other, tau=0, epsilon="auto", k=DEFAULT_K):
+        """`margin_loss` on the Python torch.autograd.Function path (ctypes onto the same C ABI)."""
+        _check_k(k, X.shape[-2])
+        need = torch.is_grad_enabled() and any(
+            torch.is_tensor(t) and t.requires_grad for t in (X, label_matrix, tau, epsilon))
+        return _MarginLossPython.apply(X, label_matrix, other, tau, epsilon, k, need)
+
     @staticmethod
     def forward(ctx, X, label_matrix, tau=0, epsilon="auto", k=DEFAULT_K):
         U = _layer_forward(ctx, X, label_matrix, tau, epsilon, k)
@@ -368,6 +381,57 @@ class _CeLossPython(torch.autograd.Function):
         need = ctx.needs_input_grad
         gX, gY, gtau, geps = _layer_backward(ctx, g, (need[0], need[1], need[3], need[4]))
         return gX, gY, None, gtau, geps, None, None
+
+
+class _MarginLossPython(torch.autograd.Function):
+    """LaplaceLearningSparseHard.margin_loss_python: the layer's Python path followed by
+    gll_margin_head_batched; the backward is _CeLossPython's."""
+
+    @staticmethod
+    def forward(ctx, X, label_matrix, other, tau, epsilon, k, need_grad):
+        if other is not None and (not torch.is_tensor(other) or other.is_floating_point()
+                                  or other.is_complex() or other.dtype == torch.bool):
+            raise TypeError("other must hold integers (or be None)")
+        U = _layer_forward(ctx, X, label_matrix, tau, epsilon, k)
+        dev, prob, B = ctx.dev, ctx.prob, ctx.B
+        m = prob.n - prob.base
+        lead = tuple(U.shape[:-2])
+        if other is not None and tuple(other.shape) != lead + (m,):
+            raise ValueError("other must have shape "
+                             + (f"B x m = {B} x {m}" if lead else f"m = {m}"))
+        with torch.cuda.device(dev):
+            o = None if other is None else \
+                other.detach().to(device=dev, dtype=torch.int64).contiguous()
+            loss = torch.empty(lead, dtype=torch.float64, device=dev)
+            moved = torch.empty(lead, dtype=torch.int64, device=dev)
+            row_margin = torch.empty(lead + (m,), dtype=torch.float64, device=dev)
+            labels = torch.empty(lead + (m,), dtype=torch.int64, device=dev)
+            second = torch.empty(lead + (m,), dtype=torch.int64, device=dev)
+            gbar = torch.empty(U.shape, dtype=torch.float32, device=dev) if need_grad else None
+            sb = _lib.lib().gll_margin_head_scratch_bytes(ct.byref(prob), B)
+            scratch = torch.empty(sb, dtype=torch.uint8, device=dev) if sb else None
+            _lib.check(_lib.lib().gll_margin_head_batched(
+                ct.byref(prob), B, ctx.ws.data_ptr(), None if o is None else o.data_ptr(),
+                loss.data_ptr(), None if gbar is None else gbar.data_ptr(),
+                row_margin.data_ptr(), labels.data_ptr(), second.data_ptr(), moved.data_ptr(),
+                None if scratch is None else scratch.data_ptr(), _stream(dev)),
+                "gll_margin_head")
+        ctx.gbar = gbar
+        out = (loss, U, labels, second, row_margin, moved)
+        if not X.is_cuda:
+            out = tuple(t.cpu() for t in out)
+        ctx.mark_non_differentiable(*out[1:])
+        return out
+
+    backward = staticmethod(_CeLossPython.backward)   # the same seven inputs, the same gbar
+
+
+def cw_margin(pred, other):
+    """The Carlini-Wagner margin in plain torch (loss2 of adversarial.py:725 without its `c`, divided
+    by the rows of `pred`): clamp(max_c pred[i, c] - pred[i, other_i], min=0).sum() / m.  The
+    yardstick of LaplaceLearningSparseHard.margin_loss, which computes it in one kernel."""
+    idx = torch.arange(pred.shape[0], device=pred.device)
+    return torch.clamp(pred.max(1)[0] - pred[idx, other], min=0).sum() / pred.shape[0]
 
 
 # ----------------------------------------------------------------------------------------

@@ -5,9 +5,9 @@ Drop-in for /root/reference/GLL.py: `from graphlearninglayer_amd import GLL` (or
 stable_conjgrad`).  Kernels live in libgll.so (csrc/, C ABI in include/gll.h).
 """
 from . import GLL  # noqa: F401
-from .GLL import (LaplaceLearningSparseHard, custom_ce_loss, knn_sym_dist,  # noqa: F401
+from .GLL import (LaplaceLearningSparseHard, custom_ce_loss, cw_margin, knn_sym_dist,  # noqa: F401
                   stable_conjgrad)
 from .parallel import gather_predictions, shard_rank_seed  # noqa: F401
 
-__all__ = ["GLL", "LaplaceLearningSparseHard", "custom_ce_loss", "knn_sym_dist", "stable_conjgrad",
-           "gather_predictions", "shard_rank_seed"]
+__all__ = ["GLL", "LaplaceLearningSparseHard", "custom_ce_loss", "cw_margin", "knn_sym_dist",
+           "stable_conjgrad", "gather_predictions", "shard_rank_seed"]

@@ -50,7 +50,8 @@ MAX_D_FEATURES = 4096            # gll_features_*: 1 <= d <= 4096 (one wave hold
 EXPORTS = (
     "gll_workspace_bytes", "gll_forward", "gll_backward", "gll_forward_batched",
     "gll_backward_batched", "gll_param_grad_scratch_bytes", "gll_param_grad_batched",
-    "gll_ce_head_scratch_bytes", "gll_ce_head_batched", "gll_graph", "gll_workspace_view",
+    "gll_ce_head_scratch_bytes", "gll_ce_head_batched", "gll_margin_head_scratch_bytes",
+    "gll_margin_head_batched", "gll_graph", "gll_workspace_view",
     "gll_cg_csr_workspace_bytes", "gll_cg_csr", "gll_prof_enable", "gll_prof_read",
     "gll_kernel_name", "gll_strerror", "gll_set_knob", "gll_build_id", "gll_select_route",
     "gll_workspace_solve_view", "gll_workspace_knn_view", "gll_gram_route",
@@ -114,6 +115,10 @@ def _declare(lib):
     lib.gll_ce_head_scratch_bytes.restype = sz
     lib.gll_ce_head_batched.argtypes = [P, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.gll_ce_head_batched.restype = i32
+    lib.gll_margin_head_scratch_bytes.argtypes = [P, i32]
+    lib.gll_margin_head_scratch_bytes.restype = sz
+    lib.gll_margin_head_batched.argtypes = [P, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.gll_margin_head_batched.restype = i32
     lib.gll_graph.argtypes = [P, vp, vp, vp]
     lib.gll_graph.restype = i32
     lib.gll_workspace_view.argtypes = [P, vp, ct.POINTER(View)]

@@ -364,6 +364,24 @@ int gll_ce_head_batched(const gll_problem* p, int B, void* ws, const int64_t* ta
                                      scratch, static_cast<hipStream_t>(stream)));
 }
 
+size_t gll_margin_head_scratch_bytes(const gll_problem* p, int B) {
+    if (check(p) != GLL_OK || B < 1 || B > 65535) return 0;
+    return ce_head_scratch_bytes(p->n - p->base, B);   // the same row partials
+}
+
+int gll_margin_head_batched(const gll_problem* p, int B, void* ws, const int64_t* other,
+                            double* loss, float* gbar, double* row_margin, int64_t* label,
+                            int64_t* second, int64_t* moved, void* scratch, void* stream) {
+    int rc = check(p);
+    if (rc != GLL_OK) return rc;
+    if (B < 1 || B > 65535) return GLL_ERR_INVALID_ARG;
+    if (!ws || !loss) return GLL_ERR_INVALID_ARG;
+    if (ce_head_scratch_bytes(p->n - p->base, B) > 0 && !scratch) return GLL_ERR_INVALID_ARG;
+    Layout L(*p);
+    return hip_status(launch_margin_head(L, B, ws, other, loss, gbar, row_margin, label, second,
+                                         moved, scratch, static_cast<hipStream_t>(stream)));
+}
+
 static int check_features(int64_t rows, int32_t d, int z_dtype, int flags) {
     if (rows < 0 || d < 1 || d > 4096) return GLL_ERR_INVALID_ARG;
     if (z_dtype != GLL_XT_F32 && z_dtype != GLL_XT_F16 && z_dtype != GLL_XT_BF16)

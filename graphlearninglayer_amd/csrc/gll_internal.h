@@ -658,6 +658,11 @@ size_t ce_head_scratch_bytes(int m, int B);
 hipError_t launch_ce_head(const Layout& L, int B, void* ws, const int64_t* targets, double* loss,
                           float* gbar, double* row_loss, int64_t* pred_label, int64_t* correct,
                           void* scratch, hipStream_t s);
+// Carlini-Wagner margin head over the same predictions (loss.hip): top-2 labels, the margin over
+// `other` (NULL: every row masked) and dloss/dU; `scratch` as the cross-entropy head's.
+hipError_t launch_margin_head(const Layout& L, int B, void* ws, const int64_t* other, double* loss,
+                              float* gbar, double* row_margin, int64_t* label, int64_t* second,
+                              int64_t* moved, void* scratch, hipStream_t s);
 // The layer's front end (features.hip): rows of fp32 / fp16 / bf16 features into fp32 rows,
 // optionally unit-norm, and the gradient's way back.  features_calls: launches so far.
 hipError_t launch_unit_rows(int64_t rows, int d, const void* Z, int z_dtype, int flags, float* X,

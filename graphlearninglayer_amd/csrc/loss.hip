@@ -1,5 +1,6 @@
-// loss.hip -- the cross-entropy head every caller of the layer puts behind it
-// (custom_ce_loss, losses.py:128-136; FullySup.py:156-171 adds the argmax accuracy).
+// loss.hip -- the heads callers of the layer put behind it: the cross-entropy head (custom_ce_loss,
+// losses.py:128-136; FullySup.py:156-171 adds the argmax accuracy) and, in the second half of the
+// file, the Carlini-Wagner margin head (adversarial.py:688-751).
 //
 // After gll_forward the workspace holds the fp32 predictions U32 (Layout::P + base * C); the
 // float64 U the forward returns is exactly double(U32) (solve.hip).  With t_i the int64 target of
@@ -278,6 +279,229 @@ hipError_t launch_ce_head(const Layout& L, int B, void* ws, const int64_t* targe
         else if (L.C <= 16) e = launch_ce<1, 16>(a, B, loss, correct, scratch, s);
         else if (L.C <= 128) e = launch_ce<16, 8>(a, B, loss, correct, scratch, s);
         else e = launch_ce<64, 4>(a, B, loss, correct, scratch, s);
+    }
+    prof_end(GLL_K_LOSS, s);
+    return e;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The Carlini-Wagner margin head (adversarial.py:688-751): the two best classes of every row, the
+// margin of the best over a class `other` the caller names, its mean and dloss/dU.  Same U32, same
+// row-holding scheme, same sums as the cross-entropy head above.  In float64, o_i = other[i]:
+//     a_i          = lowest index among the maxima of row i          (pred of the ce head)
+//     s_i          = lowest index among the maxima of the row without entry a_i;  0 for C = 1
+//     d_i          = double(U32[i, a_i]) - double(U32[i, o_i])
+//     row_margin_i = d_i when d_i >= 0 or d_i is NaN, else 0         (torch.clamp(., min=0))
+//     loss         = (sum_i row_margin_i) / m
+//     gbar[i, c]   = float(1 / m) * ([c == a_i] - [c == o_i])        a zero row when a_i == o_i
+//     moved        = #{i : a_i == o_i}
+// An o_i outside [0, C) -- or other == NULL: every row -- masks the row: margin 0, a zero gbar row,
+// not counted as moved, U never addressed with it; label and second are written all the same and
+// the divisor stays m.  The classes of a row are ranked numbers first by value descending, then
+// NaN, each by index ascending: a NaN entry is never a maximum while a number is left.
+// ------------------------------------------------------------------------------------------------
+struct MgArgs {
+    const float* U32;         // m x C of graph 0
+    const int64_t* other;     // m of graph 0, or NULL
+    float* gbar;              // m x C, or NULL
+    double* row_margin;       // m, or NULL
+    int64_t* label;           // m, or NULL
+    int64_t* second;          // m, or NULL
+    int m, C;
+    size_t ws;                // byte stride of U32 between graphs (the workspace block)
+    float ginv;               // float(1 / m)
+};
+
+// ce_load with an `other` that may be absent (-1: masked)
+template <int LPR, int NPL>
+__device__ __forceinline__ CeLoad<NPL> mg_load(const MgArgs& a, int i, int gl) {
+    const float* u = a.U32 + size_t(i) * a.C;
+    CeLoad<NPL> d;
+    d.t = a.other ? a.other[i] : int64_t(-1);
+#pragma unroll
+    for (int q = 0; q < NPL; ++q) {
+        const int c = gl + q * LPR;
+        d.v[q] = c < a.C ? u[c] : -INFINITY;
+    }
+    return d;
+}
+
+// (v1, c1) ranks before (v2, c2): value descending, NaN after every number, index ascending.
+// A total order on distinct indices; the empty slot is (NaN, INT_MAX), after every class.
+__device__ __forceinline__ bool mg_before(float v1, int c1, float v2, int c2) {
+    return v1 > v2 || (v1 == v2 && c1 < c2) || (v2 != v2 && (v1 == v1 || c1 < c2));
+}
+
+struct MgTop {
+    float v1, v2;
+    int c1, c2;   // c1 ranks before c2
+};
+
+__device__ __forceinline__ void mg_insert(MgTop& t, float v, int c) {
+    if (mg_before(v, c, t.v1, t.c1)) {
+        t.v2 = t.v1;
+        t.c2 = t.c1;
+        t.v1 = v;
+        t.c1 = c;
+    } else if (mg_before(v, c, t.v2, t.c2)) {
+        t.v2 = v;
+        t.c2 = c;
+    }
+}
+
+// The head of row i from its loaded classes (all LPR lanes of the group call this together); the
+// row's outputs are written here and the result (margin in .loss, moved in .hit) is the same on
+// every lane of the group.
+template <int LPR, int NPL>
+__device__ __forceinline__ CeRow mg_row(const MgArgs& a, int i, int gl, const CeLoad<NPL>& d) {
+    const int64_t t = d.t;
+    const bool valid = t >= 0 && t < int64_t(a.C);
+    MgTop top{NAN, NAN, INT_MAX, INT_MAX};
+    float mine = 0.f;
+#pragma unroll
+    for (int q = 0; q < NPL; ++q) {
+        const int c = gl + q * LPR;
+        if (c < a.C) mg_insert(top, d.v[q], c);
+        if (int64_t(c) == t) mine = d.v[q];
+    }
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) {   // two sorted pairs of disjoint classes into one
+        const float ov1 = __shfl_xor(top.v1, o, LPR), ov2 = __shfl_xor(top.v2, o, LPR);
+        const int oc1 = __shfl_xor(top.c1, o, LPR), oc2 = __shfl_xor(top.c2, o, LPR);
+        mg_insert(top, ov1, oc1);
+        mg_insert(top, ov2, oc2);
+    }
+    const int bc = top.c1;                          // C >= 1: a class, never the empty slot
+    const int sc = top.c2 == INT_MAX ? 0 : top.c2;  // C = 1
+    // the lane that holds class o_i hands U[i, o_i] to its group
+    const float po = LPR > 1 ? __shfl(mine, valid ? int(t % LPR) : 0, LPR) : mine;
+    CeRow r{0.0, 0};
+    if (valid) {   // group-uniform
+        const double dd = double(top.v1) - double(po);
+        r.loss = (dd >= 0.0 || dd != dd) ? dd : 0.0;
+        r.hit = int64_t(bc) == t;
+    }
+    if (a.gbar) {
+        float* g = a.gbar + size_t(i) * a.C;
+        const bool live = valid && !r.hit;
+#pragma unroll
+        for (int q = 0; q < NPL; ++q) {
+            const int c = gl + q * LPR;
+            if (c < a.C) g[c] = !live ? 0.f : c == bc ? a.ginv : int64_t(c) == t ? -a.ginv : 0.f;
+        }
+    }
+    if (gl == 0) {
+        if (a.row_margin) a.row_margin[i] = r.loss;
+        if (a.label) a.label[i] = int64_t(bc);
+        if (a.second) a.second[i] = int64_t(sc);
+    }
+    return r;
+}
+
+__device__ __forceinline__ void mg_to_graph(MgArgs& a, int g) {
+    a.U32 = gshift_at(a.U32, a.ws, g);
+    a.other = gshift_at(a.other, size_t(a.m) * sizeof(int64_t), g);
+    a.gbar = gshift_at(a.gbar, size_t(a.m) * a.C * sizeof(float), g);
+    a.row_margin = gshift_at(a.row_margin, size_t(a.m) * sizeof(double), g);
+    a.label = gshift_at(a.label, size_t(a.m) * sizeof(int64_t), g);
+    a.second = gshift_at(a.second, size_t(a.m) * sizeof(int64_t), g);
+}
+
+// The single-launch form (ce_head_kernel's): workgroup g is graph g, group q the rows q, q + G, ...
+template <int LPR, int NPL>
+__global__ __launch_bounds__(kCeThreads) void margin_head_kernel(MgArgs a,
+                                                                 double* __restrict__ loss,
+                                                                 int64_t* __restrict__ moved) {
+    const int g = blockIdx.x;
+    mg_to_graph(a, g);
+    constexpr int G = kCeThreads / LPR;
+    const int q = threadIdx.x / LPR, gl = threadIdx.x % LPR;
+    double s = 0.0;
+    int hits = 0;
+    for (int i = q; i < a.m; i += G) {   // group-uniform trip count
+        const CeRow r = mg_row<LPR, NPL>(a, i, gl, mg_load<LPR, NPL>(a, i, gl));
+        s += r.loss;
+        hits += r.hit;
+    }
+    if (gl != 0) {
+        s = 0.0;
+        hits = 0;
+    }
+    ce_finish<kCeThreads>(s, hits, a.m, g, loss, moved);
+}
+
+// Past kCeOneWg rows: one row per group into ce_rows_kernel's parts layout (m float64 margins, then
+// m int32 moved flags a graph); ce_reduce_kernel sums them.
+template <int LPR, int NPL>
+__global__ __launch_bounds__(256) void margin_rows_kernel(MgArgs a, double* __restrict__ parts,
+                                                          size_t pss) {
+    const int g = blockIdx.y;
+    mg_to_graph(a, g);
+    parts = gshift_at(parts, pss, g);
+    constexpr int G = 256 / LPR;
+    const int gl = threadIdx.x % LPR;
+    const int i = blockIdx.x * G + threadIdx.x / LPR;
+    if (i >= a.m) return;   // group-uniform
+    const CeRow r = mg_row<LPR, NPL>(a, i, gl, mg_load<LPR, NPL>(a, i, gl));
+    if (gl == 0) {
+        parts[i] = r.loss;
+        reinterpret_cast<int*>(parts + a.m)[i] = r.hit;
+    }
+}
+
+__global__ void margin_zero_kernel(double* __restrict__ loss, int64_t* __restrict__ moved, int B) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < B) {
+        loss[g] = 0.0;
+        if (moved) moved[g] = 0;
+    }
+}
+
+template <int LPR, int NPL>
+static hipError_t launch_mg(const MgArgs& a, int B, double* loss, int64_t* moved, void* scratch,
+                            hipStream_t s) {
+    if (a.m <= kCeOneWg) {
+        launch_k(margin_head_kernel<LPR, NPL>, dim3(B), kCeThreads, 0, s, a, loss, moved);
+        return launch_status("loss.hip:margin_head_kernel");
+    }
+    const size_t pss = ce_parts_stride(a.m);
+    double* parts = static_cast<double*>(scratch);
+    constexpr unsigned G = 256 / LPR;
+    prof_span(2);
+    launch_k(margin_rows_kernel<LPR, NPL>, dim3((unsigned(a.m) + G - 1) / G, B), 256, 0, s, a,
+             parts, pss);
+    hipError_t e = launch_status("loss.hip:margin_rows_kernel");
+    if (e != hipSuccess) return e;
+    launch_k(ce_reduce_kernel, dim3(B), 256, 0, s, static_cast<const double*>(parts), pss, a.m,
+             loss, moved);
+    return launch_status("loss.hip:ce_reduce_kernel");
+}
+
+hipError_t launch_margin_head(const Layout& L, int B, void* ws, const int64_t* other, double* loss,
+                              float* gbar, double* row_margin, int64_t* label, int64_t* second,
+                              int64_t* moved, void* scratch, hipStream_t s) {
+    prof_begin(GLL_K_LOSS, s);
+    hipError_t e;
+    if (L.m == 0) {   // no unlabeled row: loss = 0, moved = 0, nothing else
+        launch_k(margin_zero_kernel, dim3((unsigned(B) + 255) / 256), 256, 0, s, loss, moved, B);
+        e = launch_status("loss.hip:margin_zero_kernel");
+    } else {
+        MgArgs a;
+        a.U32 = L.at<float>(ws, L.P) + size_t(L.base) * L.C;
+        a.other = other;
+        a.gbar = gbar;
+        a.row_margin = row_margin;
+        a.label = label;
+        a.second = second;
+        a.m = L.m;
+        a.C = L.C;
+        a.ws = L.total;
+        a.ginv = float(1.0 / double(L.m));
+        // the ce head's lanes per row x classes per lane
+        if (L.C <= 4) e = launch_mg<1, 4>(a, B, loss, moved, scratch, s);
+        else if (L.C <= 16) e = launch_mg<1, 16>(a, B, loss, moved, scratch, s);
+        else if (L.C <= 128) e = launch_mg<16, 8>(a, B, loss, moved, scratch, s);
+        else e = launch_mg<64, 4>(a, B, loss, moved, scratch, s);
     }
     prof_end(GLL_K_LOSS, s);
     return e;

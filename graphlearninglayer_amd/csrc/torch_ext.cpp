@@ -17,6 +17,9 @@
 //     by the cross-entropy head (gll_ce_head_batched: custom_ce_loss of losses.py:128-136 and the
 //     argmax accuracy of FullySup.py:156-171 in one kernel); its node is the same one, holding
 //     the head's dloss/dU;
+//   * `margin_loss(X, label_matrix, other, tau=0, epsilon='auto', k=25, normalize=False)` is the
+//     same call followed by the Carlini-Wagner margin head (gll_margin_head_batched: the top-2
+//     labels and the clamped margin of adversarial.py:688-751 in one kernel), on the same node;
 //   * the front end: an fp32 X with normalize=False goes to the kernels as it is;
 //     normalize=True, or an fp16 / bf16 X, takes one gll_features_forward launch into a fresh fp32
 //     X^ (and rnorm), which the node saves instead of X, and one gll_features_backward launch that
@@ -287,7 +290,8 @@ struct LaplaceBackward : public torch::autograd::Node {
     int n_inputs_ = 1;
     GradLike Y_, tau_, eps_;
     bool Y_shared_ = false;   // 2-D label_matrix with batched X: the gradient sums over graphs
-    at::Tensor gbar_;         // ce_loss: dloss/dU (fp32, U's shape); the node's output is the loss
+    at::Tensor gbar_;         // ce_loss / margin_loss: dloss/dU (fp32, U's shape); the node's
+                              // output is the loss
 
     std::string name() const override { return "LaplaceLearningSparseHardBackward"; }
 
@@ -627,6 +631,36 @@ PyObject* apply_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames)
     return THPVariable_Wrap(c.X.is_cuda() ? std::move(c.U) : c.U.cpu());
 }
 
+// What the loss heads (ce_loss, margin_loss) share around their kernel.
+// One int64 per unlabeled row on the device, from a tensor of integers of shape m (B x m with a
+// batched X).
+at::Tensor head_rows_arg(const LayerCall& c, const at::Tensor& T, const char* what) {
+    const int64_t m = c.n - c.base;
+    const bool shape_ok = c.batched ? (T.dim() == 2 && T.size(0) == c.B && T.size(1) == m)
+                                    : (T.dim() == 1 && T.size(0) == m);
+    if (!shape_ok)
+        raise_py(PyExc_ValueError, std::string(what) + " must have shape " +
+                                       (c.batched ? "B x m = " + std::to_string(c.B) + " x " : "m = ") +
+                                       std::to_string(m));
+    return T.detach().to(c10::Device(c10::kCUDA, c.devi), at::kLong).contiguous();
+}
+
+// The result tuple of a head; out[0] is the loss.  When a gradient is wanted (gbar defined) the
+// loss takes the layer's node, which keeps the head's dloss/dU.
+PyObject* head_result(LayerCall& c, const std::vector<at::Tensor>& inputs, at::Tensor gbar,
+                      std::vector<at::Tensor> out) {
+    if (gbar.defined()) {
+        auto node = make_node(c, inputs);
+        node->gbar_ = std::move(gbar);
+        torch::autograd::set_history(out[0], node);
+    }
+    PyObject* tup = PyTuple_New(Py_ssize_t(out.size()));
+    if (!tup) throw PyErrSet{};
+    for (size_t q = 0; q < out.size(); ++q)
+        PyTuple_SET_ITEM(tup, q, THPVariable_Wrap(c.X.is_cuda() ? out[q] : out[q].cpu()));
+    return tup;
+}
+
 // ------------------------------------------------------------------------------------------
 // ce_loss(X, label_matrix, targets, tau=0, epsilon='auto', k=25, normalize=False): the layer and the
 // cross-entropy head its callers put behind it (losses.py:128-136, FullySup.py:156-171) in one
@@ -645,14 +679,7 @@ PyObject* ce_loss_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwname
     LayerCall c;
     layer_forward(c, "ce_loss", a[0], a[1], a[3], a[4], a[5], a[6]);
     const int64_t m = c.n - c.base;
-    const bool shape_ok = c.batched ? (T.dim() == 2 && T.size(0) == c.B && T.size(1) == m)
-                                    : (T.dim() == 1 && T.size(0) == m);
-    if (!shape_ok)
-        raise_py(PyExc_ValueError, std::string("targets must have shape ") +
-                                       (c.batched ? "B x m = " + std::to_string(c.B) + " x " : "m = ") +
-                                       std::to_string(m));
-    const c10::Device dev(c10::kCUDA, c.devi);
-    at::Tensor Td = T.detach().to(dev, at::kLong).contiguous();
+    at::Tensor Td = head_rows_arg(c, T, "targets");
     const auto f64 = c.X32.options().dtype(at::kDouble);
     const auto i64 = c.X32.options().dtype(at::kLong);
     const std::vector<int64_t> one = c.batched ? std::vector<int64_t>{c.B} : std::vector<int64_t>{};
@@ -672,17 +699,54 @@ PyObject* ce_loss_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwname
                                  correct.data_ptr<int64_t>(),
                                  sb ? scratch.data_ptr() : nullptr, c.s),
              "gll_ce_head");
-    if (need_grad) {
-        auto node = make_node(c, inputs);
-        node->gbar_ = std::move(gbar);
-        torch::autograd::set_history(loss, node);
+    return head_result(c, inputs, gbar, {loss, c.U, labels, row_loss, correct});
+}
+
+// ------------------------------------------------------------------------------------------
+// margin_loss(X, label_matrix, other, tau=0, epsilon='auto', k=25, normalize=False): the layer and
+// the Carlini-Wagner margin its attack loop puts behind it (adversarial.py:688-751) in one call.
+// gll_margin_head_batched writes the two best classes of every row, the margin of the best over
+// `other`, its mean, the count of rows whose best class is `other` and -- when a gradient is
+// wanted -- dloss/dU for the same node ce_loss uses.  other = None: the top-2 query alone.
+// ------------------------------------------------------------------------------------------
+PyObject* margin_loss_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames) {
+    static const char* names[] = {"X", "label_matrix", "other", "tau", "epsilon", "k", "normalize"};
+    PyObject* a[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    collect_args("margin_loss", names, 7, args, nargs, kwnames, a);
+    if (!a[2]) raise_py(PyExc_TypeError, "margin_loss() needs other (a tensor of integers or None)");
+    at::Tensor T;   // undefined: other = None
+    if (a[2] != Py_None) {
+        T = tensor_arg(a[2], "other");
+        if (!at::isIntegralType(T.scalar_type(), false))
+            raise_py(PyExc_TypeError, "other must hold integers (or be None)");
     }
-    at::Tensor out[5] = {loss, c.U, labels, row_loss, correct};
-    PyObject* tup = PyTuple_New(5);
-    if (!tup) throw PyErrSet{};
-    for (int q = 0; q < 5; ++q)
-        PyTuple_SET_ITEM(tup, q, THPVariable_Wrap(c.X.is_cuda() ? out[q] : out[q].cpu()));
-    return tup;
+    LayerCall c;
+    layer_forward(c, "margin_loss", a[0], a[1], a[3], a[4], a[5], a[6]);
+    const int64_t m = c.n - c.base;
+    at::Tensor Td;
+    if (T.defined()) Td = head_rows_arg(c, T, "other");
+    const auto f64 = c.X32.options().dtype(at::kDouble);
+    const auto i64 = c.X32.options().dtype(at::kLong);
+    const std::vector<int64_t> one = c.batched ? std::vector<int64_t>{c.B} : std::vector<int64_t>{};
+    const std::vector<int64_t> rows = c.batched ? std::vector<int64_t>{c.B, m} : std::vector<int64_t>{m};
+    at::Tensor loss = at::empty(one, f64), moved = at::empty(one, i64);
+    at::Tensor row_margin = at::empty(rows, f64);
+    at::Tensor labels = at::empty(rows, i64), second = at::empty(rows, i64);
+    const std::vector<at::Tensor> inputs = grad_inputs(c);
+    const bool need_grad = torch::autograd::compute_requires_grad(inputs);
+    at::Tensor gbar, scratch;
+    if (need_grad) gbar = at::empty(c.U.sizes(), c.X32.options());
+    const size_t sb = gll_margin_head_scratch_bytes(&c.p, int(c.B));
+    if (sb) scratch = at::empty({int64_t(sb)}, c.X32.options().dtype(at::kByte));
+    check_rc(gll_margin_head_batched(&c.p, int(c.B), c.ws.data_ptr(),
+                                     Td.defined() ? Td.data_ptr<int64_t>() : nullptr,
+                                     loss.data_ptr<double>(),
+                                     need_grad ? gbar.data_ptr<float>() : nullptr,
+                                     row_margin.data_ptr<double>(), labels.data_ptr<int64_t>(),
+                                     second.data_ptr<int64_t>(), moved.data_ptr<int64_t>(),
+                                     sb ? scratch.data_ptr() : nullptr, c.s),
+             "gll_margin_head");
+    return head_result(c, inputs, gbar, {loss, c.U, labels, second, row_margin, moved});
 }
 
 template <PyObject* (*Impl)(PyObject* const*, Py_ssize_t, PyObject*)>
@@ -720,6 +784,19 @@ PyMethodDef kCeLossDef = {
     "(FullySup.py:156-171) with one extra kernel.  Only loss is differentiable (with respect to\n"
     "the inputs apply differentiates); a target outside [0, C) leaves its row out"};
 
+PyMethodDef kMarginLossDef = {
+    "margin_loss",
+    reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(entry_py<margin_loss_impl>)),
+    METH_FASTCALL | METH_KEYWORDS,
+    "loss, pred, labels, second, row_margin, moved =\n"
+    "    LaplaceLearningSparseHard.margin_loss(X, label_matrix, other, tau=0, epsilon='auto', k=25,\n"
+    "                                          normalize=False)\n"
+    "apply followed by the Carlini-Wagner margin (adversarial.py:688-751) with one extra kernel:\n"
+    "the best and second-best class of every row, row_margin = clamp(max - pred[i, other_i], 0),\n"
+    "loss = row_margin.sum() / m and moved = #{labels == other}.  Only loss is differentiable (with\n"
+    "respect to the inputs apply differentiates); an other_i outside [0, C) leaves its row out and\n"
+    "other=None leaves every row out (the top-2 query alone)"};
+
 // ------------------------------------------------------------------------------------------
 // status API for the Python layer
 // ------------------------------------------------------------------------------------------
@@ -740,6 +817,9 @@ PYBIND11_MODULE(_gll_torch, m) {
                               PyCFunction_NewEx(&kApplyDef, nullptr, m.attr("__name__").ptr())));
     m.add_object("ce_loss", pybind11::reinterpret_steal<pybind11::object>(
                                 PyCFunction_NewEx(&kCeLossDef, nullptr, m.attr("__name__").ptr())));
+    m.add_object("margin_loss",
+                 pybind11::reinterpret_steal<pybind11::object>(
+                     PyCFunction_NewEx(&kMarginLossDef, nullptr, m.attr("__name__").ptr())));
     m.def("status_sink", [](int dev) { return int64_t(status_of(dev).sink.data_ptr()); },
           "device address of the sticky status words of device `dev` (gll_problem.status_sink)");
     m.def("note_call", [](int dev) {

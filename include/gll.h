@@ -202,6 +202,41 @@ int gll_ce_head_batched(const gll_problem* p, int B, void* workspace, const int6
                         double* loss, float* gbar, double* row_loss, int64_t* pred_label,
                         int64_t* correct, void* scratch, void* stream);
 
+/* Carlini-Wagner margin head: replaces what the attack loop of adversarial.py:688-751 computes
+ * from the layer's output in PyTorch -- the two best classes of every row (its argmax, the -1e6
+ * edit, argmax again) and loss2 = clamp(max(output, 1)[0] - output[idx, other], min=0).sum() --
+ * read from the fp32 predictions gll_forward left in the workspace, as the cross-entropy head
+ * does.  With m = n - base, o_i = other[g*m + i] and everything evaluated in float64:
+ *   label_i      = a_i = lowest index among the maxima of row i   (pred_label of the ce head)
+ *   second_i     = s_i = lowest index among the maxima of the row with entry a_i removed (what
+ *                  the -1e6 edit finds); 0 for C = 1
+ *   d_i          = double(U32[i, a_i]) - double(U32[i, o_i])
+ *   row_margin_i = d_i when d_i >= 0 or d_i is NaN, else 0     (torch.clamp propagates NaN)
+ *   loss[g]      = (sum_i row_margin_i) / m      (the caller applies its own c and divisor: the
+ *                  reference divides by len(target) = base + m)
+ *   gbar[i, c]   = float(1/m) * ([c == a_i] - [c == o_i])   fp32 m x C, dense; a zero row when
+ *                  a_i == o_i.  d_i >= 0 by construction, so the clamp never cuts a finite row
+ *                  and the gradient passes wherever PyTorch's passes
+ *   moved[g]     = #{i : a_i == o_i}             rows the attack has already flipped
+ * Ranking: numbers by value descending, NaN entries after every number, each by index ascending;
+ * a row of NaN has label 0 and second 1.  An o_i outside [0, C) masks its row: margin 0, a zero
+ * gbar row, not counted in moved, U never addressed with it (U[i, o_i] is picked from the
+ * registers that hold the row); label and second are written all the same and the divisor stays
+ * m.  other == NULL masks every row: a pure top-2 query, the attack's set-up step.  Call after
+ * gll_forward(_batched) on the same workspace(s) and problem.  other: B x m int64; loss: B
+ * float64; gbar: B x m x C fp32; row_margin: B x m float64; label, second: B x m int64; moved: B
+ * int64 -- all device memory, all but loss may be NULL.  `scratch`:
+ * gll_margin_head_scratch_bytes(p, B) bytes (0 for m <= 4096: one launch, grid = B; past that a
+ * row pass plus a reduce).  The sum runs in a fixed order that depends on (m, C) alone: no
+ * atomics, bitwise reproducible, and graph g of a batch equals the single call.  m == 0 writes
+ * loss = 0 and moved = 0 and nothing else.  Timed under GLL_K_LOSS. */
+size_t gll_margin_head_scratch_bytes(const gll_problem* p, int B);
+int gll_margin_head_batched(const gll_problem* p, int B, void* workspace,
+                            const int64_t* other /* B x m, may be NULL = all masked */,
+                            double* loss, float* gbar, double* row_margin,
+                            int64_t* label, int64_t* second, int64_t* moved,
+                            void* scratch, void* stream);
+
 /* Graph only (the device half of knn_sym_dist, GLL.py:180-244): kNN search, symmetric
  * CSR, eps, weights and degrees into the workspace; no solve.  Requires p->base == 0
  * (no labeled block; size the workspace for that problem).  Read the arrays with
