@@ -30,11 +30,13 @@ FLAG_D2_F32 = 131072      # fp32 distance matrix on the pre-split Gram route
 FLAG_ROW_ORDER_OFF = 262144   # large single graphs: row-index order instead of the locality order
 # process-wide test knobs (gll_set_knob): force a code path, 0 = automatic
 KNOB_VR_RV, KNOB_GRID_CAP, KNOB_GRAM_TILE, KNOB_SEL_FORM, KNOB_GRAM_TAIL, KNOB_ROW_PRE = 0, 1, 2, 3, 4, 5
+KNOB_GRAD_SPLIT = 6   # fused backward: long rows in feature parts (0 automatic, 1 on, 2 off)
 ST_TINY_EPS, ST_FWD_NONCONV, ST_FWD_ITERS, ST_BWD_NONCONV, ST_BWD_ITERS = 0, 1, 2, 3, 4
 ST_KNN_RESCAN = 5   # kNN rows re-ranked over every column under the Gram error bound
 ST_SOLVE_FAILED = 6   # the fused backward gave up on its adjoint solves: grad NaN, raised
 ST_GRID_RESCUED = 10  # whole-GPU CG solves rescued by one workgroup after a lost grid barrier
 ST_KNN_MERGE = 7   # kNN rows that took the full-row select fallback (diagnostic)
+ST_GRAD_SPLIT = 12  # rows the last fused backward ran as 2 or 4 waves over feature parts (diagnostic)
 ST_NWORDS = 16
 K_GRAM, K_SELECT, K_FINALIZE, K_CG, K_EDGE, K_GRAD = range(6)
 K_BWD = 6     # cg_grad_fused_kernel
@@ -55,7 +57,7 @@ EXPORTS = (
     "gll_cg_csr_workspace_bytes", "gll_cg_csr", "gll_prof_enable", "gll_prof_read",
     "gll_kernel_name", "gll_strerror", "gll_set_knob", "gll_build_id", "gll_select_route",
     "gll_workspace_solve_view", "gll_workspace_knn_view", "gll_gram_route",
-    "gll_features_forward", "gll_features_backward", "gll_features_calls",
+    "gll_features_forward", "gll_features_backward", "gll_features_calls", "gll_fused_plan",
 )
 
 
@@ -141,6 +143,8 @@ def _declare(lib):
     lib.gll_kernel_name.restype = ct.c_char_p
     lib.gll_select_route.argtypes = [ct.POINTER(Problem), i32, i32, i32, ct.POINTER(ct.c_int32)]
     lib.gll_select_route.restype = i32
+    lib.gll_fused_plan.argtypes = [ct.POINTER(Problem), i32, i32, ct.POINTER(ct.c_int32)]
+    lib.gll_fused_plan.restype = i32
     lib.gll_set_knob.argtypes = [i32, i32]
     lib.gll_set_knob.restype = i32
     lib.gll_strerror.argtypes = [i32]

@@ -264,7 +264,7 @@ static int backward_impl(const gll_problem* p, int B, const float* X, void* ws,
         const hipError_t e = launch_cg_grad_fused(L, ws, gbar, g_dtype, X, p->eps, gradX, rtol,
                                                   max_iter, st + GLL_ST_BWD_NONCONV,
                                                   st + GLL_ST_BWD_ITERS, st + GLL_ST_SOLVE_FAILED,
-                                                  vec_ok(X, p->d), s);
+                                                  st + GLL_ST_GRAD_SPLIT, vec_ok(X, p->d), s);
         if (e != hipErrorNotSupported) return hip_status(e);
     }
     // adjoint solve: Luu is symmetric, so Luu^-T gbar = Luu^-1 gbar (GLL.py:93)
@@ -578,6 +578,19 @@ int gll_select_route(const gll_problem* p, int B, int x_aligned, int rows,
         select_table_index(rt), select_table_rows()};
     for (int q = 0; q < GLL_SEL_ROUTE_WORDS; ++q) out[q] = words[q];
     return words[10] >= 0 ? GLL_OK : GLL_ERR_UNSUPPORTED;
+}
+
+int gll_fused_plan(const gll_problem* p, int x_aligned, int capacity,
+                   int32_t out[GLL_FUSED_PLAN_WORDS]) {
+    int rc = check(p);
+    if (rc != GLL_OK) return rc;
+    if (!out) return GLL_ERR_INVALID_ARG;
+    Layout L(*p);
+    if (capacity < 0)   // the current device's: an occupancy query
+        return fused_plan_device(L, p->eps, x_aligned && p->d % 4 == 0, GLL_DT_F64, out)
+                   ? GLL_OK : GLL_ERR_UNSUPPORTED;
+    return fused_plan(L, p->eps, x_aligned && p->d % 4 == 0, capacity, out) ? GLL_OK
+                                                                             : GLL_ERR_UNSUPPORTED;
 }
 
 #ifndef GLL_BUILD_ID

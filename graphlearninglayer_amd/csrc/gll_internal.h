@@ -618,6 +618,7 @@ hipError_t launch_finalize(const Layout& L, const Batch& bt, void* ws, const voi
                            int y_dtype, float tau, float eps_fixed, hipStream_t s);
 // b: right-hand sides of graph 0, `b_stride` bytes apart (the workspace rhs or gbar)
 // st_failed: the public GLL_ST_SOLVE_FAILED word (whole-GPU CG barrier failure)
+// st_split: the public GLL_ST_GRAD_SPLIT word (fused backward; may be NULL)
 hipError_t launch_cg_luu(const Layout& L, const Batch& bt, void* ws, const void* b,
                          size_t b_stride, int b_dtype, double* out64, float* out32, float rtol,
                          int max_iter, int32_t* st_nonconv, int32_t* st_iters,
@@ -644,7 +645,11 @@ hipError_t launch_backward_grad(const Layout& L, const Batch& bt, void* ws, cons
 hipError_t launch_cg_grad_fused(const Layout& L, void* ws, const void* gbar, int g_dtype,
                                 const float* X, float eps_fixed, float* gradX, float rtol,
                                 int max_iter, int32_t* st_nonconv, int32_t* st_iters,
-                                int32_t* st_failed, bool vec, hipStream_t s);
+                                int32_t* st_failed, int32_t* st_split, bool vec, hipStream_t s);
+// That launch's sizes for `capacity` co-resident workgroups (gll_fused_plan, include/gll.h).
+bool fused_plan(const Layout& L, float eps_fixed, bool vec, int64_t capacity, int32_t out[8]);
+// The same for the current device's capacity (an occupancy query; no launch).
+bool fused_plan_device(const Layout& L, float eps_fixed, bool vec, int g_dtype, int32_t out[8]);
 // Gradients of label_matrix / tau / fixed eps from the workspace a backward left behind
 // (param_grad.hip): `what` GLL_PG_* bits, `scratch` param_grad_scratch_bytes(n, B) bytes of
 // float64 row partials (only read and written when a scalar is selected).

@@ -57,6 +57,9 @@ extern "C" {
 #define GLL_ST_GRID_RESCUED 10 /* whole-GPU CG solves whose grid barrier timed out (a workgroup
                                 * was not resident: other kernels held the CUs) and that one
                                 * workgroup then solved alone -- correct, slower (count) */
+#define GLL_ST_GRAD_SPLIT 12   /* rows the last fused backward (cg_grad_fused_kernel) ran as 2 or 4
+                                * waves, each over a part of the row's features (diagnostic: the
+                                * gradient is bitwise the same either way; 0 when rows ran whole) */
 #define GLL_ST_NWORDS 16
 
 /* gll_problem.flags: code-path choices for tests and A/B runs; none changes a result beyond
@@ -102,7 +105,10 @@ extern "C" {
 #define GLL_KNOB_GRAM_TAIL 4  /* 256-tile Gram's short last round: 1 none, 2 as 128-subtiles
                                * instead of 64-subtiles (gram.hip launch_gram) */
 #define GLL_KNOB_ROW_PRE 5    /* row build label prefetch: 1 on, 2 off (rows.hip) */
-#define GLL_KNOB_COUNT 6
+#define GLL_KNOB_GRAD_SPLIT 6 /* fused backward: long rows in feature parts: 0 automatic (on where
+                               * a row holds more than one f32x4 per lane, d > 256), 1 the same,
+                               * 2 off: the launch of one wave per row (solve.hip) */
+#define GLL_KNOB_COUNT 7
 int gll_set_knob(int knob, int value);
 
 typedef struct gll_problem {
@@ -389,6 +395,20 @@ const char* gll_kernel_name(int kid);
 #define GLL_SEL_ROUTE_WORDS 12
 int gll_select_route(const gll_problem* p, int B, int x_aligned, int rows,
                      int32_t out[GLL_SEL_ROUTE_WORDS]);
+
+/* Diagnostic: the launch of the fused backward (cg_grad_fused_kernel) for this problem on a
+ * device that holds `capacity` of its workgroups at once (occupancy x compute units), x_aligned as
+ * above.  With capacity >= 0 no HIP call: it runs without a GPU, and the launcher sizes its launch
+ * from the same record.  out[0] = threads per workgroup, out[1] = f32x4 vectors a lane holds of a feature row
+ * (1, 2, 4), out[2] = workgroups launched, out[3] = the base grid C + ceil(n / waves per
+ * workgroup) the route requires to be co-resident, out[4] = gradient waves, out[5] = spare waves
+ * (out[4] - n) that take the parts of long rows, out[6] = 1 when rows may run in parts, out[7] =
+ * dynamic LDS bytes.  GLL_ERR_UNSUPPORTED when the backward takes two launches instead.  Reads
+ * GLL_KNOB_GRAD_SPLIT.  capacity < 0: the current device's (this form does query HIP: the
+ * occupancy of the kernel a float64 grad_output runs; the float32 one has the same resources). */
+#define GLL_FUSED_PLAN_WORDS 8
+int gll_fused_plan(const gll_problem* p, int x_aligned, int capacity,
+                   int32_t out[GLL_FUSED_PLAN_WORDS]);
 
 /* Build identity: sha256 (16 hex) of the sources, headers and flags this library was built
  * from (graphlearninglayer_amd/build.py source_digest).  bench.py cites only profiles
