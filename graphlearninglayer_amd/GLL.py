@@ -25,6 +25,11 @@ Deliberate differences from the reference (all documented in DESIGN.md):
   * LaplaceLearningSparseHard.margin_loss(X, label_matrix, other, ...) is apply followed by the
     Carlini-Wagner attack's top-2 labels and clamped margin (adversarial.py:688-751) with one
     extra kernel (gll_margin_head_batched, DESIGN.md §3.9);
+  * LaplaceLearningSparseHard.objective(X, label_matrix, targets, ..., weights, score, score_out,
+    indices) is apply followed by the head of a score-driven step (FullySup.py:156-175): the
+    weighted cross-entropy / entropy / l2 loss (losses.py:128-136, :100-101, :111-112) and the
+    per-sample score scattered into a device store, with one extra kernel
+    (gll_objective_head_batched, DESIGN.md §3.10);
   * label_matrix (floating point), tau and a fixed epsilon are differentiable as well as X
     (the reference returns None for them, GLL.py:177): tau / epsilon may be one-element
     tensors, whose value is read once in the forward (a host sync when on the GPU), and their
@@ -232,6 +237,18 @@ class LaplaceLearningSparseHard(torch.autograd.Function):
             torch.is_tensor(t) and t.requires_grad for t in (X, label_matrix, tau, epsilon))
         return _MarginLossPython.apply(X, label_matrix, other, tau, epsilon, k, need)
 
+    objective = staticmethod(_ext_mod.objective)
+
+    @classmethod
+    def objective_python(cls, X, label_matrix, targets, tau=0, epsilon="auto", k=DEFAULT_K,
+                         weights=(1.0, 0.0, 0.0), score=None, score_out=None, indices=None):
+        """`objective` on the Python torch.autograd.Function path (ctypes onto the same C ABI)."""
+        _check_k(k, X.shape[-2])
+        need = torch.is_grad_enabled() and any(
+            torch.is_tensor(t) and t.requires_grad for t in (X, label_matrix, tau, epsilon))
+        return _ObjectivePython.apply(X, label_matrix, targets, tau, epsilon, k, need, weights,
+                                      score, score_out, indices)
+
     @staticmethod
     def forward(ctx, X, label_matrix, tau=0, epsilon="auto", k=DEFAULT_K):
         U = _layer_forward(ctx, X, label_matrix, tau, epsilon, k)
@@ -424,6 +441,87 @@ class _MarginLossPython(torch.autograd.Function):
         return out
 
     backward = staticmethod(_CeLossPython.backward)   # the same seven inputs, the same gbar
+
+
+_SCORE_KINDS = {None: _lib.SCORE_NONE, "entropy": _lib.SCORE_ENTROPY, "l2": _lib.SCORE_L2}
+
+
+class _ObjectivePython(torch.autograd.Function):
+    """LaplaceLearningSparseHard.objective_python: the layer's Python path followed by
+    gll_objective_head_batched; the backward is _CeLossPython's."""
+
+    @staticmethod
+    def forward(ctx, X, label_matrix, targets, tau, epsilon, k, need_grad, weights, score,
+                score_out, indices):
+        if targets is not None and (not torch.is_tensor(targets) or targets.is_floating_point()
+                                    or targets.is_complex() or targets.dtype == torch.bool):
+            raise TypeError("targets must hold integers (or be None)")
+        try:
+            w_ce, w_ent, w_l2 = (float(w) for w in weights)
+        except (TypeError, ValueError):
+            raise ValueError("weights must be three numbers (w_ce, w_ent, w_l2)") from None
+        if isinstance(score, torch.Tensor) or score not in _SCORE_KINDS:
+            raise ValueError("score must be None, 'entropy' or 'l2'")
+        kind = _SCORE_KINDS[score]
+        if (score_out is None) != (indices is None):
+            raise ValueError("score_out and indices go together: give both or neither")
+        if score_out is not None and kind == _lib.SCORE_NONE:
+            raise ValueError("score_out needs score='entropy' or score='l2'")
+        dev = _device_for(X)
+        if score_out is not None:
+            if not torch.is_tensor(score_out) or score_out.dtype != torch.float32 \
+                    or score_out.dim() != 1 or not score_out.is_contiguous() \
+                    or score_out.device != dev:
+                raise ValueError("score_out must be a contiguous float32 tensor of shape N on the "
+                                 "layer's device")
+            if not torch.is_tensor(indices) or indices.is_floating_point() \
+                    or indices.is_complex() or indices.dtype == torch.bool:
+                raise TypeError("indices must hold integers")
+        else:
+            kind = _lib.SCORE_NONE   # a score without a store: nothing to scatter
+        U = _layer_forward(ctx, X, label_matrix, tau, epsilon, k)
+        prob, B = ctx.prob, ctx.B
+        m = prob.n - prob.base
+        lead = tuple(U.shape[:-2])
+        for name, v in (("targets", targets), ("indices", indices)):
+            if v is not None and tuple(v.shape) != lead + (m,):
+                raise ValueError(f"{name} must have shape "
+                                 + (f"B x m = {B} x {m}" if lead else f"m = {m}"))
+        with torch.cuda.device(dev):
+            def rows_arg(v):
+                return None if v is None else \
+                    v.detach().to(device=dev, dtype=torch.int64).contiguous()
+
+            t, ind = rows_arg(targets), rows_arg(indices)
+            f64 = dict(dtype=torch.float64, device=dev)
+            i64 = dict(dtype=torch.int64, device=dev)
+            loss, correct = torch.empty(lead, **f64), torch.empty(lead, **i64)
+            row_loss, row_ent, row_l2 = (torch.empty(lead + (m,), **f64) for _ in range(3))
+            labels = torch.empty(lead + (m,), **i64)
+            gbar = torch.empty(U.shape, dtype=torch.float32, device=dev) if need_grad else None
+            sb = _lib.lib().gll_objective_head_scratch_bytes(ct.byref(prob), B)
+            scratch = torch.empty(sb, dtype=torch.uint8, device=dev) if sb else None
+
+            def ptr(v):
+                return None if v is None else v.data_ptr()
+
+            _lib.check(_lib.lib().gll_objective_head_batched(
+                ct.byref(prob), B, ctx.ws.data_ptr(), ptr(t), w_ce, w_ent, w_l2, loss.data_ptr(),
+                ptr(gbar), row_loss.data_ptr(), row_ent.data_ptr(), row_l2.data_ptr(),
+                labels.data_ptr(), correct.data_ptr(), kind, ptr(score_out),
+                0 if score_out is None else score_out.shape[0], ptr(ind), ptr(scratch),
+                _stream(dev)), "gll_objective_head")
+        ctx.gbar = gbar
+        out = (loss, U, labels, row_loss, correct, row_ent, row_l2)
+        if not X.is_cuda:
+            out = tuple(o.cpu() for o in out)
+        ctx.mark_non_differentiable(*out[1:])
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_loss, *_):
+        # ce_loss's seven inputs first, then weights, score, score_out, indices
+        return (*_CeLossPython.backward(ctx, grad_loss), None, None, None, None)
 
 
 def cw_margin(pred, other):

@@ -44,7 +44,8 @@ K_PARAM = 7   # param_grad_kernel: label_matrix / tau / eps gradients
 K_LOSS = 8    # ce_head_kernel: cross-entropy head (gll_ce_head_batched)
 K_COUNT = 9
 PG_Y, PG_TAU, PG_EPS = 1, 2, 4   # gll_param_grad_batched `what` bits
-XT_F32, XT_F16, XT_BF16 = 0, 1, 2   # gll_features_* element types of Z / gZ
+SCORE_NONE, SCORE_ENTROPY, SCORE_L2 = 0, 1, 2   # gll_objective_head_batched score_kind
+XT_F32, XT_F16, XT_BF16 = 0, 1, 2  # gll_features_* element types of Z / gZ
 UF_NORMALIZE = 1                 # gll_features_* flag: unit-norm rows
 MAX_D_FEATURES = 4096            # gll_features_*: 1 <= d <= 4096 (one wave holds a row)
 
@@ -58,6 +59,7 @@ EXPORTS = (
     "gll_kernel_name", "gll_strerror", "gll_set_knob", "gll_build_id", "gll_select_route",
     "gll_workspace_solve_view", "gll_workspace_knn_view", "gll_gram_route",
     "gll_features_forward", "gll_features_backward", "gll_features_calls", "gll_fused_plan",
+    "gll_objective_head_scratch_bytes", "gll_objective_head_batched",
 )
 
 
@@ -121,6 +123,12 @@ def _declare(lib):
     lib.gll_margin_head_scratch_bytes.restype = sz
     lib.gll_margin_head_batched.argtypes = [P, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.gll_margin_head_batched.restype = i32
+    lib.gll_objective_head_scratch_bytes.argtypes = [P, i32]
+    lib.gll_objective_head_scratch_bytes.restype = sz
+    f64 = ct.c_double
+    lib.gll_objective_head_batched.argtypes = [P, i32, vp, vp, f64, f64, f64, vp, vp, vp, vp, vp,
+                                               vp, vp, i32, vp, ct.c_int64, vp, vp, vp]
+    lib.gll_objective_head_batched.restype = i32
     lib.gll_graph.argtypes = [P, vp, vp, vp]
     lib.gll_graph.restype = i32
     lib.gll_workspace_view.argtypes = [P, vp, ct.POINTER(View)]

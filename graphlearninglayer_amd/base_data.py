@@ -21,6 +21,10 @@ call site: `next(iter(provider))` yields one (images, labels) batch like the Dat
 and `label_matrix()` gives the one-hot float matrix FullySup.py:153 builds for
 `LaplaceLearningSparseHard.apply`.  `update()` replaces the base set when the caller
 re-selects it (FullySup.py:278).
+
+`DeviceScoreStore` is the device-resident side of that re-selection: the per-sample scores of
+DatasetWithScore (utils.py:751-812) and its `select_base_data` choice as dataset indices, which
+the caller gathers and hands to `DeviceBaseLoader.update`.
 """
 from __future__ import annotations
 
@@ -104,3 +108,95 @@ class DeviceBaseLoader:
                 raise RuntimeError("label_matrix(): no draw yet -- pass the labels of the batch")
             labels = self._last_labels
         return torch.nn.functional.one_hot(labels, num_classes=self.num_classes).float()
+
+
+class DeviceScoreStore:
+    """The score store and base selection of DatasetWithScore (utils.py:751-812) without the
+    images: per-sample scores in device memory and `select_indices`, which returns the dataset
+    indices `select_base_data` would stack -- the caller gathers its own resident data with them
+    and hands the result to `DeviceBaseLoader.update(data[idx], labels[idx])`.
+
+    labels: N integer class labels of the training set
+    device: where the store lives (default: the current CUDA device, else the CPU)
+    seed:   seeds the store's own generator for mode='random' (None: nondeterministic)
+
+    `scores` (float32 zeros of shape N) is what `LaplaceLearningSparseHard.objective` takes as
+    `score_out`: the layer call then writes the step's scores itself and the reference's
+    per-sample `update_score` loop (FullySup.py:174-175) disappears.  The class order is the
+    order of first appearance in `labels`, the insertion order of prepare_class_indices.
+    """
+
+    def __init__(self, labels, device=None, seed=None):
+        if device is None:
+            device = (torch.device("cuda", torch.cuda.current_device())
+                      if torch.cuda.is_available() else torch.device("cpu"))
+        self.device = torch.device(device)
+        labels = torch.as_tensor(labels)
+        if labels.dim() != 1:
+            raise ValueError("labels must have shape N")
+        if labels.dtype.is_floating_point or labels.dtype == torch.bool:
+            raise TypeError("labels must be integer class indices")
+        self.labels = labels.to(self.device, torch.int64).contiguous()
+        n = self.labels.shape[0]
+        self.scores = torch.zeros(n, dtype=torch.float32, device=self.device)
+        self._gen = torch.Generator(device=self.device)
+        if seed is None:
+            self._gen.seed()
+        else:
+            self._gen.manual_seed(int(seed))
+        # classes by first appearance; each class's indices ascending (set-up, done once)
+        uniq, inv = torch.unique(self.labels, return_inverse=True)
+        first = torch.full((uniq.shape[0],), n, dtype=torch.int64, device=self.device)
+        first.scatter_reduce_(0, inv, torch.arange(n, device=self.device), reduce="amin")
+        self.classes = uniq[torch.argsort(first)]
+        self.class_indices = [torch.nonzero(self.labels == c).flatten()
+                              for c in self.classes.tolist()]
+
+    def __len__(self) -> int:
+        return int(self.scores.shape[0])
+
+    def update_score(self, index, new_score) -> None:
+        """scores[index] = new_score for a whole batch at once (utils.py:765-766 takes one
+        sample per call): one index_put_, no host synchronisation for device arguments."""
+        index = torch.as_tensor(index).to(self.device, torch.int64)
+        new_score = torch.as_tensor(new_score).detach().to(self.device, torch.float32)
+        self.scores.index_put_((index,), new_score)
+
+    def _by_score(self, idx, count):
+        """The first `count` of `idx` (ascending dataset indices) by score descending; equal
+        scores keep ascending index (Python's stable sorted(..., reverse=True)); NaN after every
+        number, -inf included."""
+        s = self.scores.index_select(0, idx)
+        nan = torch.isnan(s)
+        # torch.sort ranks NaN first when descending: rank it as -inf, then move it behind -inf
+        # with a second stable sort on the flag; + 0.0 makes -0.0 tie with 0.0 as Python does
+        key = torch.where(nan, torch.full_like(s, float("-inf")), s) + 0.0
+        order = torch.sort(key, descending=True, stable=True).indices
+        order = order[torch.sort(nan[order].to(torch.uint8), stable=True).indices]
+        return idx.index_select(0, order[:count])
+
+    def _at_random(self, idx, count):
+        perm = torch.randperm(idx.shape[0], device=self.device, generator=self._gen)
+        return idx.index_select(0, perm[:count])
+
+    def select_indices(self, num_samples, class_uniform_sample=False, mode="random"):
+        """int64 dataset indices of the next base set (select_base_data, utils.py:768-792).
+        mode='score': the highest scores; mode='random': uniform without replacement from the
+        store's generator.  class_uniform_sample: num_samples // (classes present) per class --
+        the whole class where it is smaller -- classes concatenated in first-appearance order."""
+        if mode == "score":
+            pick = self._by_score
+        elif mode == "random":
+            pick = self._at_random
+        else:
+            raise ValueError(mode)
+        num_samples = int(num_samples)
+        if not class_uniform_sample:
+            if mode == "random" and num_samples > len(self):   # random.sample raises too
+                raise ValueError("sample larger than the population")
+            return pick(torch.arange(len(self), device=self.device), max(num_samples, 0))
+        per_class = num_samples // max(len(self.class_indices), 1)
+        parts = [pick(idx, min(per_class, idx.shape[0])) for idx in self.class_indices]
+        if not parts:
+            return torch.empty(0, dtype=torch.int64, device=self.device)
+        return torch.cat(parts)

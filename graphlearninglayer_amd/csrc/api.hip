@@ -382,6 +382,32 @@ int gll_margin_head_batched(const gll_problem* p, int B, void* ws, const int64_t
                                          moved, scratch, static_cast<hipStream_t>(stream)));
 }
 
+size_t gll_objective_head_scratch_bytes(const gll_problem* p, int B) {
+    if (check(p) != GLL_OK || B < 1 || B > 65535) return 0;
+    return ce_head_scratch_bytes(p->n - p->base, B);   // the same row partials
+}
+
+int gll_objective_head_batched(const gll_problem* p, int B, void* ws, const int64_t* targets,
+                               double w_ce, double w_ent, double w_l2, double* loss, float* gbar,
+                               double* row_ce, double* row_entropy, double* row_l2,
+                               int64_t* pred_label, int64_t* correct, int score_kind,
+                               float* score_out, int64_t score_len, const int64_t* indices,
+                               void* scratch, void* stream) {
+    int rc = check(p);
+    if (rc != GLL_OK) return rc;
+    if (B < 1 || B > 65535) return GLL_ERR_INVALID_ARG;
+    if (!ws || !loss) return GLL_ERR_INVALID_ARG;
+    if (score_kind < GLL_SCORE_NONE || score_kind > GLL_SCORE_L2) return GLL_ERR_INVALID_ARG;
+    if (score_kind != GLL_SCORE_NONE && (!score_out || !indices || score_len < 0))
+        return GLL_ERR_INVALID_ARG;
+    if (ce_head_scratch_bytes(p->n - p->base, B) > 0 && !scratch) return GLL_ERR_INVALID_ARG;
+    Layout L(*p);
+    return hip_status(launch_objective_head(L, B, ws, targets, w_ce, w_ent, w_l2, loss, gbar,
+                                            row_ce, row_entropy, row_l2, pred_label, correct,
+                                            score_kind, score_out, score_len, indices, scratch,
+                                            static_cast<hipStream_t>(stream)));
+}
+
 static int check_features(int64_t rows, int32_t d, int z_dtype, int flags) {
     if (rows < 0 || d < 1 || d > 4096) return GLL_ERR_INVALID_ARG;
     if (z_dtype != GLL_XT_F32 && z_dtype != GLL_XT_F16 && z_dtype != GLL_XT_BF16)

@@ -668,6 +668,15 @@ hipError_t launch_ce_head(const Layout& L, int B, void* ws, const int64_t* targe
 hipError_t launch_margin_head(const Layout& L, int B, void* ws, const int64_t* other, double* loss,
                               float* gbar, double* row_margin, int64_t* label, int64_t* second,
                               int64_t* moved, void* scratch, hipStream_t s);
+// Score/objective head over the same predictions (loss.hip): cross-entropy, entropy and l2 terms
+// under three weights, the per-row scores and their scatter into `score_out` (score_kind 0: none);
+// `scratch` as the cross-entropy head's.
+hipError_t launch_objective_head(const Layout& L, int B, void* ws, const int64_t* targets,
+                                 double w_ce, double w_ent, double w_l2, double* loss, float* gbar,
+                                 double* row_ce, double* row_entropy, double* row_l2,
+                                 int64_t* pred_label, int64_t* correct, int score_kind,
+                                 float* score_out, int64_t score_len, const int64_t* indices,
+                                 void* scratch, hipStream_t s);
 // The layer's front end (features.hip): rows of fp32 / fp16 / bf16 features into fp32 rows,
 // optionally unit-norm, and the gradient's way back.  features_calls: launches so far.
 hipError_t launch_unit_rows(int64_t rows, int d, const void* Z, int z_dtype, int flags, float* X,

@@ -20,6 +20,10 @@
 //   * `margin_loss(X, label_matrix, other, tau=0, epsilon='auto', k=25, normalize=False)` is the
 //     same call followed by the Carlini-Wagner margin head (gll_margin_head_batched: the top-2
 //     labels and the clamped margin of adversarial.py:688-751 in one kernel), on the same node;
+//   * `objective(X, label_matrix, targets, ..., weights, score, score_out, indices)` is the same
+//     call followed by the score/objective head (gll_objective_head_batched: the weighted
+//     cross-entropy / entropy / l2 loss and the score store of FullySup.py:165-175 in one kernel),
+//     on the same node;
 //   * the front end: an fp32 X with normalize=False goes to the kernels as it is;
 //     normalize=True, or an fp16 / bf16 X, takes one gll_features_forward launch into a fresh fp32
 //     X^ (and rnorm), which the node saves instead of X, and one gll_features_backward launch that
@@ -749,6 +753,101 @@ PyObject* margin_loss_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kw
     return head_result(c, inputs, gbar, {loss, c.U, labels, second, row_margin, moved});
 }
 
+// ------------------------------------------------------------------------------------------
+// objective(X, label_matrix, targets, tau=0, epsilon='auto', k=25, normalize=False,
+//           weights=(1, 0, 0), score=None, score_out=None, indices=None): the layer and the
+// score-driven training step's head (FullySup.py:156-175) in one call.
+// gll_objective_head_batched writes the weighted cross-entropy / entropy / l2 loss, the per-row
+// terms, labels, the correct count, the chosen score scattered into `score_out` at `indices`
+// and -- when a gradient is wanted -- dloss/dU for the same node ce_loss uses.
+// targets = None: every row masked (the regularisers alone).
+// ------------------------------------------------------------------------------------------
+PyObject* objective_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames) {
+    static const char* names[] = {"X", "label_matrix", "targets", "tau", "epsilon", "k",
+                                  "normalize", "weights", "score", "score_out", "indices"};
+    PyObject* a[11] = {};
+    collect_args("objective", names, 11, args, nargs, kwnames, a);
+    if (!a[2]) raise_py(PyExc_TypeError, "objective() needs targets (a tensor of integers or None)");
+    at::Tensor T;   // undefined: targets = None
+    if (a[2] != Py_None) {
+        T = tensor_arg(a[2], "targets");
+        if (!at::isIntegralType(T.scalar_type(), false))
+            raise_py(PyExc_TypeError, "targets must hold integers (or be None)");
+    }
+    double w[3] = {1.0, 0.0, 0.0};
+    if (a[7] && a[7] != Py_None) {
+        PyObject* seq = PySequence_Fast(a[7], "weights must be three numbers (w_ce, w_ent, w_l2)");
+        if (!seq) throw PyErrSet{};
+        const bool three = PySequence_Fast_GET_SIZE(seq) == 3;
+        for (int q = 0; three && q < 3; ++q) {
+            w[q] = PyFloat_AsDouble(PySequence_Fast_GET_ITEM(seq, q));
+            if (w[q] == -1.0 && PyErr_Occurred()) {
+                Py_DECREF(seq);
+                throw PyErrSet{};
+            }
+        }
+        Py_DECREF(seq);
+        if (!three) raise_py(PyExc_ValueError, "weights must be three numbers (w_ce, w_ent, w_l2)");
+    }
+    int kind = GLL_SCORE_NONE;
+    if (a[8] && a[8] != Py_None) {
+        const char* sk = PyUnicode_Check(a[8]) ? PyUnicode_AsUTF8(a[8]) : nullptr;
+        if (sk && std::strcmp(sk, "entropy") == 0) kind = GLL_SCORE_ENTROPY;
+        else if (sk && std::strcmp(sk, "l2") == 0) kind = GLL_SCORE_L2;
+        else raise_py(PyExc_ValueError, "score must be None, 'entropy' or 'l2'");
+    }
+    const bool has_out = a[9] && a[9] != Py_None, has_idx = a[10] && a[10] != Py_None;
+    if (has_out != has_idx)
+        raise_py(PyExc_ValueError, "score_out and indices go together: give both or neither");
+    if (has_out && kind == GLL_SCORE_NONE)
+        raise_py(PyExc_ValueError, "score_out needs score='entropy' or score='l2'");
+    at::Tensor S, I;
+    if (has_out) {
+        S = tensor_arg(a[9], "score_out");
+        I = tensor_arg(a[10], "indices");
+        if (S.scalar_type() != at::kFloat || S.dim() != 1 || !S.is_contiguous() || !S.is_cuda())
+            raise_py(PyExc_ValueError,
+                     "score_out must be a contiguous float32 tensor of shape N on the layer's device");
+        if (!at::isIntegralType(I.scalar_type(), false))
+            raise_py(PyExc_TypeError, "indices must hold integers");
+    } else {
+        kind = GLL_SCORE_NONE;   // a score without a store: nothing to scatter
+    }
+    LayerCall c;
+    layer_forward(c, "objective", a[0], a[1], a[3], a[4], a[5], a[6]);
+    if (has_out && S.device().index() != c.devi)
+        raise_py(PyExc_ValueError,
+                 "score_out must be a contiguous float32 tensor of shape N on the layer's device");
+    const int64_t m = c.n - c.base;
+    at::Tensor Td, Id;
+    if (T.defined()) Td = head_rows_arg(c, T, "targets");
+    if (has_out) Id = head_rows_arg(c, I, "indices");
+    const auto f64 = c.X32.options().dtype(at::kDouble);
+    const auto i64 = c.X32.options().dtype(at::kLong);
+    const std::vector<int64_t> one = c.batched ? std::vector<int64_t>{c.B} : std::vector<int64_t>{};
+    const std::vector<int64_t> rows = c.batched ? std::vector<int64_t>{c.B, m} : std::vector<int64_t>{m};
+    at::Tensor loss = at::empty(one, f64), correct = at::empty(one, i64);
+    at::Tensor row_loss = at::empty(rows, f64), row_ent = at::empty(rows, f64);
+    at::Tensor row_l2 = at::empty(rows, f64), labels = at::empty(rows, i64);
+    const std::vector<at::Tensor> inputs = grad_inputs(c);
+    const bool need_grad = torch::autograd::compute_requires_grad(inputs);
+    at::Tensor gbar, scratch;
+    if (need_grad) gbar = at::empty(c.U.sizes(), c.X32.options());
+    const size_t sb = gll_objective_head_scratch_bytes(&c.p, int(c.B));
+    if (sb) scratch = at::empty({int64_t(sb)}, c.X32.options().dtype(at::kByte));
+    check_rc(gll_objective_head_batched(
+                 &c.p, int(c.B), c.ws.data_ptr(), Td.defined() ? Td.data_ptr<int64_t>() : nullptr,
+                 w[0], w[1], w[2], loss.data_ptr<double>(),
+                 need_grad ? gbar.data_ptr<float>() : nullptr, row_loss.data_ptr<double>(),
+                 row_ent.data_ptr<double>(), row_l2.data_ptr<double>(),
+                 labels.data_ptr<int64_t>(), correct.data_ptr<int64_t>(), kind,
+                 has_out ? S.data_ptr<float>() : nullptr, has_out ? S.size(0) : 0,
+                 has_out ? Id.data_ptr<int64_t>() : nullptr, sb ? scratch.data_ptr() : nullptr,
+                 c.s),
+             "gll_objective_head");
+    return head_result(c, inputs, gbar, {loss, c.U, labels, row_loss, correct, row_ent, row_l2});
+}
+
 template <PyObject* (*Impl)(PyObject* const*, Py_ssize_t, PyObject*)>
 PyObject* entry_py(PyObject*, PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames) {
     try {
@@ -797,6 +896,21 @@ PyMethodDef kMarginLossDef = {
     "respect to the inputs apply differentiates); an other_i outside [0, C) leaves its row out and\n"
     "other=None leaves every row out (the top-2 query alone)"};
 
+PyMethodDef kObjectiveDef = {
+    "objective",
+    reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(entry_py<objective_impl>)),
+    METH_FASTCALL | METH_KEYWORDS,
+    "loss, pred, pred_labels, row_loss, correct, row_entropy, row_l2 =\n"
+    "    LaplaceLearningSparseHard.objective(X, label_matrix, targets, tau=0, epsilon='auto', k=25,\n"
+    "                                        normalize=False, weights=(1.0, 0.0, 0.0),\n"
+    "                                        score=None, score_out=None, indices=None)\n"
+    "apply followed by the head of a score-driven training step (FullySup.py:156-175) with one\n"
+    "extra kernel: loss = (w_ce sum(ce) + w_ent sum(entropy) - w_l2 sum(pred^2)) / m for weights =\n"
+    "(w_ce, w_ent, w_l2) (losses.py:128-136, :100-101, :111-112), row_l2 = 1 - sum(pred^2, 1), and\n"
+    "score_out[indices] = row_loss ('entropy') or row_l2 ('l2') as float32, written in place.  Only\n"
+    "loss is differentiable; a target outside [0, C) leaves its row out of the ce term, of correct\n"
+    "and of the scatter, targets=None leaves every row out; an index outside score_out is skipped"};
+
 // ------------------------------------------------------------------------------------------
 // status API for the Python layer
 // ------------------------------------------------------------------------------------------
@@ -820,7 +934,10 @@ PYBIND11_MODULE(_gll_torch, m) {
     m.add_object("margin_loss",
                  pybind11::reinterpret_steal<pybind11::object>(
                      PyCFunction_NewEx(&kMarginLossDef, nullptr, m.attr("__name__").ptr())));
-    m.def("status_sink", [](int dev) { return int64_t(status_of(dev).sink.data_ptr()); },
+    m.add_object("objective",
+                 pybind11::reinterpret_steal<pybind11::object>(
+                     PyCFunction_NewEx(&kObjectiveDef, nullptr, m.attr("__name__").ptr())));
+    m.def("status_sink",[](int dev) { return int64_t(status_of(dev).sink.data_ptr()); },
           "device address of the sticky status words of device `dev` (gll_problem.status_sink)");
     m.def("note_call", [](int dev) {
               with_py_errors([&] {

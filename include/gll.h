@@ -243,6 +243,52 @@ int gll_margin_head_batched(const gll_problem* p, int B, void* workspace,
                             int64_t* label, int64_t* second, int64_t* moved,
                             void* scratch, void* stream);
 
+/* Score/objective head: the cross-entropy head plus what a score-driven training step takes from
+ * the same predictions -- the regularisers for unlabeled rows (losses.py:100-101 entropy,
+ * :111-112 l2), the per-sample scores of FullySup.py:165-173 and their store
+ * (train_dataset.update_score, one Python iteration per sample in the reference).  Read from the
+ * fp32 predictions gll_forward left in the workspace, as the other heads do.  With m = n - base,
+ * u_c = double(U32[i, c]), t_i = targets[g*m + i] and everything evaluated in float64:
+ *   p_i      = u_{t_i} + 1e-8
+ *   ce_i     = -log(p_i)                      t_i outside [0, C): masked, ce_i = 0
+ *   ent_i    = -sum_c u_c log(u_c + 1e-8)
+ *   sq_i     = sum_c u_c^2
+ *   loss[g]  = (sum_i (w_ce ce_i + w_ent ent_i - w_l2 sq_i)) / m
+ *   gbar[i, c] = float((1/m) (w_ce (-1/p_i) [c == t_i]
+ *                             - w_ent (log(u_c + 1e-8) + u_c / (u_c + 1e-8)) - w_l2 2 u_c))
+ *   row_ce = ce_i, row_entropy = ent_i, row_l2 = 1 - sq_i (the l2 score of FullySup.py:171),
+ *   pred_label and correct as the cross-entropy head's.
+ * No clamp: where PyTorch's formula gives NaN or inf, so does this.  A term whose weight is exactly
+ * 0 is not evaluated and contributes exactly 0, even where it would be NaN: w = (1, 0, 0) is the
+ * cross-entropy head, bitwise.  Masking by target touches the ce term, row_ce and correct alone --
+ * ent_i and sq_i are computed for every row (regularising rows without a label is what they are
+ * for) -- and the divisor stays m.  targets == NULL masks every row.
+ * Score scatter: score_kind GLL_SCORE_ENTROPY stores ce_i, GLL_SCORE_L2 stores row_l2_i:
+ * score_out[indices[g*m + i]] = float(score_i) for every row that is not masked and whose index
+ * lies in [0, score_len); the index forms an address only after that test and a target never does.
+ * Duplicate indices within one call are the caller's error: one of the candidate values is stored,
+ * which one is not specified.  One score_out (score_len fp32) serves all B graphs.
+ * Call after gll_forward(_batched) on the same workspace(s) and problem.  targets, indices: B x m
+ * int64; loss: B float64; gbar: B x m x C fp32; row_ce, row_entropy, row_l2: B x m float64;
+ * pred_label: B x m int64; correct: B int64 -- all device memory, all but loss may be NULL
+ * (score_out and indices only with GLL_SCORE_NONE).  `scratch`:
+ * gll_objective_head_scratch_bytes(p, B) bytes (0 for m <= 4096: one launch, one workgroup a graph
+ * -- plus helper workgroups that write row_entropy when it is an output only, w_ent == 0; past
+ * that a row pass plus a reduce).  The sums over rows run in the cross-entropy head's fixed order, over
+ * the per-row combined term: no atomics, bitwise reproducible, and graph g of a batch equals the
+ * single call.  m == 0 writes loss = 0 and nothing else.  Timed under GLL_K_LOSS. */
+#define GLL_SCORE_NONE    0
+#define GLL_SCORE_ENTROPY 1   /* -log(pred[i, t_i] + 1e-8), FullySup.py:169 */
+#define GLL_SCORE_L2      2   /* 1 - sum(pred[i]^2), FullySup.py:171 */
+size_t gll_objective_head_scratch_bytes(const gll_problem* p, int B);
+int gll_objective_head_batched(const gll_problem* p, int B, void* workspace,
+                               const int64_t* targets /* B x m, may be NULL = all masked */,
+                               double w_ce, double w_ent, double w_l2,
+                               double* loss, float* gbar, double* row_ce, double* row_entropy,
+                               double* row_l2, int64_t* pred_label, int64_t* correct,
+                               int score_kind, float* score_out, int64_t score_len,
+                               const int64_t* indices, void* scratch, void* stream);
+
 /* Graph only (the device half of knn_sym_dist, GLL.py:180-244): kNN search, symmetric
  * CSR, eps, weights and degrees into the workspace; no solve.  Requires p->base == 0
  * (no labeled block; size the workspace for that problem).  Read the arrays with
