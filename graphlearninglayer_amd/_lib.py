@@ -48,6 +48,25 @@ SCORE_NONE, SCORE_ENTROPY, SCORE_L2 = 0, 1, 2   # gll_objective_head_batched sco
 XT_F32, XT_F16, XT_BF16 = 0, 1, 2  # gll_features_* element types of Z / gZ
 UF_NORMALIZE = 1                 # gll_features_* flag: unit-norm rows
 MAX_D_FEATURES = 4096            # gll_features_*: 1 <= d <= 4096 (one wave holds a row)
+SC_ALL, SC_ONE = 0, 1            # gll_supcon_* mode
+# supcon.hip tiling (csrc/gll_internal.h kSc*): an MFMA tile is SC_TILE x SC_TILE logits, a
+# workgroup owns SC_ROWS anchor rows and one chunk of column tiles, features go SC_KC at a time
+SC_TILE, SC_ROWS, SC_KC, SC_TARGET_WG, SC_PART_BYTES, SC_MIN_BUDGET = 32, 64, 128, 512, 32, 3 << 20
+SC_TARGET_WG_FWD = 1024
+SC_MAX_ROWS = 65536
+
+
+def supcon_plan(rows: int, d: int):
+    """(column tiles, row blocks, chunks, tiles per chunk, forward chunks, tiles per forward
+    chunk) of gll_supcon_* for (rows, d): the host-side mirror of supcon.hip supcon_plan;
+    gll_supcon_scratch_bytes = 32 rows fchunks + 4 d rows chunks, the second term only for
+    chunks > 1."""
+    ntiles, rowblocks = -(-rows // SC_TILE), -(-rows // SC_ROWS)
+    per = rows * (4 * d + SC_PART_BYTES)
+    nc = max(1, min(-(-SC_TARGET_WG // rowblocks), max(2 * rows * rows, SC_MIN_BUDGET) // per, ntiles))
+    tpc = -(-ntiles // nc)
+    ftpc = -(-ntiles // min(-(-SC_TARGET_WG_FWD // rowblocks), ntiles))
+    return ntiles, rowblocks, -(-ntiles // tpc), tpc, -(-ntiles // ftpc), ftpc
 
 # every symbol include/gll.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -60,6 +79,7 @@ EXPORTS = (
     "gll_workspace_solve_view", "gll_workspace_knn_view", "gll_gram_route",
     "gll_features_forward", "gll_features_backward", "gll_features_calls", "gll_fused_plan",
     "gll_objective_head_scratch_bytes", "gll_objective_head_batched",
+    "gll_supcon_scratch_bytes", "gll_supcon_forward", "gll_supcon_backward", "gll_supcon_launches",
 )
 
 
@@ -165,6 +185,17 @@ def _declare(lib):
     lib.gll_features_backward.restype = i32
     lib.gll_features_calls.argtypes = []
     lib.gll_features_calls.restype = ct.c_int64
+    f32 = ct.c_float
+    lib.gll_supcon_scratch_bytes.argtypes = [ct.c_int64, ct.c_int32]
+    lib.gll_supcon_scratch_bytes.restype = sz
+    lib.gll_supcon_forward.argtypes = [ct.c_int64, ct.c_int32, ct.c_int32, vp, vp, i32, f32, f32,
+                                       vp, vp, vp, vp, vp]
+    lib.gll_supcon_forward.restype = i32
+    lib.gll_supcon_backward.argtypes = [ct.c_int64, ct.c_int32, ct.c_int32, vp, vp, i32, f32, f32,
+                                        vp, vp, vp, vp, vp]
+    lib.gll_supcon_backward.restype = i32
+    lib.gll_supcon_launches.argtypes = []
+    lib.gll_supcon_launches.restype = ct.c_int64
     return lib
 
 

@@ -5,6 +5,7 @@
 // Python mirror takes it from torch's caching allocator) and keeps it alive from
 // gll_forward to gll_backward, as the reference keeps its graph on ctx (GLL.py:69-70).
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
@@ -437,6 +438,46 @@ int gll_features_backward(int64_t rows, int32_t d, const float* gX, const float*
 }
 
 int64_t gll_features_calls(void) { return features_calls(); }
+
+static int check_supcon(int64_t rows, int32_t V, int32_t d, int mode, float T, float Tb) {
+    if (rows < 2 || V < 1 || d < 1 || rows % V != 0) return GLL_ERR_INVALID_ARG;
+    if (mode != GLL_SC_ALL && mode != GLL_SC_ONE) return GLL_ERR_INVALID_ARG;
+    if (!(T > 0.f) || !(Tb > 0.f) || !std::isfinite(T) || !std::isfinite(Tb))
+        return GLL_ERR_INVALID_ARG;
+    if (rows > 65536 || d > 4096) return GLL_ERR_UNSUPPORTED;
+    return GLL_OK;
+}
+
+size_t gll_supcon_scratch_bytes(int64_t rows, int32_t d) {
+    if (rows < 2 || rows > 65536 || d < 1 || d > 4096) return 0;
+    return supcon_scratch_bytes(rows, d);
+}
+
+int gll_supcon_forward(int64_t rows, int32_t V, int32_t d, const float* Z, const int64_t* labels,
+                       int mode, float T, float Tb, double* loss, float* row_loss, float* stats,
+                       void* scratch, void* stream) {
+    const int rc = check_supcon(rows, V, d, mode, T, Tb);
+    if (rc != GLL_OK) return rc;
+    if (!Z || !loss || !stats || !scratch) return GLL_ERR_INVALID_ARG;
+    if (reinterpret_cast<uintptr_t>(Z) % 4 || reinterpret_cast<uintptr_t>(scratch) % 8)
+        return GLL_ERR_INVALID_ARG;
+    return hip_status(launch_supcon_forward(rows, V, d, Z, labels, mode, T, Tb, loss, row_loss,
+                                            stats, scratch, static_cast<hipStream_t>(stream)));
+}
+
+int gll_supcon_backward(int64_t rows, int32_t V, int32_t d, const float* Z, const int64_t* labels,
+                        int mode, float T, float Tb, const float* stats, const double* grad_loss,
+                        float* gZ, void* scratch, void* stream) {
+    const int rc = check_supcon(rows, V, d, mode, T, Tb);
+    if (rc != GLL_OK) return rc;
+    if (!Z || !stats || !grad_loss || !gZ || !scratch) return GLL_ERR_INVALID_ARG;
+    if (reinterpret_cast<uintptr_t>(Z) % 4 || reinterpret_cast<uintptr_t>(scratch) % 8)
+        return GLL_ERR_INVALID_ARG;
+    return hip_status(launch_supcon_backward(rows, V, d, Z, labels, mode, T, Tb, stats, grad_loss,
+                                             gZ, scratch, static_cast<hipStream_t>(stream)));
+}
+
+int64_t gll_supcon_launches(void) { return supcon_launches(); }
 
 int gll_workspace_view(const gll_problem* p, void* ws, gll_view* out) {
     int rc = check(p);

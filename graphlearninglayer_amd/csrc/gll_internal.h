@@ -684,5 +684,31 @@ hipError_t launch_unit_rows(int64_t rows, int d, const void* Z, int z_dtype, int
 hipError_t launch_unit_grad(int64_t rows, int d, const float* gX, const float* X,
                             const float* rnorm, int flags, void* gZ, int z_dtype, hipStream_t s);
 int64_t features_calls();
+// Fused SupCon / SimCLR loss (supcon.hip).  A workgroup of kScWaves waves owns
+// kScRows anchor rows (one kScTile-row MFMA tile per wave) and a chunk of `tpc` column tiles of
+// kScTile rows; features are staged kScKc at a time.  supcon_plan is a function of (rows, d)
+// alone: about kScTargetWg workgroups, the chunk scratch held to max(2 rows^2, kScMinBudget) B
+// (backward: `chunks` of `tpc` tiles); the forward, whose partials are 32 B a row, cuts finer
+// (`fchunks` of `ftpc` tiles, about kScTargetWgFwd workgroups).
+constexpr int kScTile = 32;
+constexpr int kScWaves = 2;
+constexpr int kScRows = kScTile * kScWaves;
+constexpr int kScKc = 128;
+constexpr int kScTargetWg = 512;
+constexpr int kScTargetWgFwd = 1024;
+constexpr int kScPartBytes = 32;                   // (max, sum exp, sum pos, count) as float64
+constexpr int64_t kScMinBudget = int64_t(3) << 20;
+struct ScPlan {
+    int ntiles, rowblocks, chunks, tpc, fchunks, ftpc;
+};
+ScPlan supcon_plan(int64_t rows, int d);
+size_t supcon_scratch_bytes(int64_t rows, int d);
+hipError_t launch_supcon_forward(int64_t R, int V, int d, const float* Z, const int64_t* labels,
+                                 int mode, float T, float Tb, double* loss, float* row_loss,
+                                 float* stats, void* scratch, hipStream_t s);
+hipError_t launch_supcon_backward(int64_t R, int V, int d, const float* Z, const int64_t* labels,
+                                  int mode, float T, float Tb, const float* stats,
+                                  const double* grad_loss, float* gZ, void* scratch, hipStream_t s);
+int64_t supcon_launches();
 
 }  // namespace gll

@@ -497,6 +497,52 @@ int gll_features_backward(int64_t rows, int32_t d, const float* gX, const float*
                           const float* rnorm, int flags, void* gZ, int z_dtype, void* stream);
 int64_t gll_features_calls(void);  /* launches of either kernel so far in this process (host counter) */
 
+/* Fused SupCon / SimCLR loss (losses.py:11-98: SupConLoss, and SimCLR with labels == NULL), its
+ * forward and its gradient, without the R x R logits ever in memory.  Z is the contiguous
+ * features tensor [bsz, V, d] in memory order: row r = b V + v is view v of sample b, R = rows =
+ * bsz V.  lab(r) = labels[r / V], or r / V when labels is NULL.  Row r is an anchor always
+ * (GLL_SC_ALL) or when v == 0 (GLL_SC_ONE); A = R or bsz anchors.  For an anchor r:
+ *   l_rj   = (z_r . z_j) / T                       every j in [0, R)
+ *   m_r    = max_j l_rj                            (the diagonal included, losses.py:73)
+ *   E_r    = sum_{j != r} exp(l_rj - m_r)
+ *   pos(r) = { j != r : lab(j) == lab(r) },  c_r = |pos(r)|,  P_r = sum_{j in pos(r)} l_rj
+ *   row_loss_r = -(T / Tb) (P_r / c_r - m_r - log E_r)
+ *   loss   = (sum_{anchors r} row_loss_r) / A
+ * and with gl = *grad_loss
+ *   q_rj   = (1 / (A Tb)) ([j != r] exp(l_rj - m_r) / E_r - [j in pos(r)] / c_r)  for an anchor r, else 0
+ *   gZ_r   = gl sum_j (q_rj + q_jr) z_j
+ * No clamps: an anchor with c_r = 0 gives 0/0, a NaN loss and an all-NaN gZ, as the reference
+ * does.  Labels are only compared for equality (any int64 value).  The contract covers logits
+ * whose spread m_r - l_rj stays inside the fp32 exp range (unit-norm rows at T >= 0.03 always
+ * do); outside it the reference underflows to +-inf and this implementation may stay finite.
+ * The explicit mask= of losses.py:29-30 is not built.
+ *
+ * Forward: two launches.  `stats` (rows x 4 floats) receives per row (m_r, log E_r, c_r, 1/E_r),
+ * of every row, anchor or not; row_loss (A floats, may be NULL) the anchors' losses in the
+ * reference's order (view-major: v bsz + b; GLL_SC_ONE: b); *loss the float64 loss.  Backward:
+ * two launches, from the same Z, labels and the forward's stats; gZ is rows x d fp32.
+ * The dot products run on the fp32-input MFMA (bit-for-bit an fmaf chain over the features);
+ * the row sums are float64; no atomics: every sum order depends on (rows, V, d, mode) alone, so
+ * two runs are bitwise equal.  `scratch`: gll_supcon_scratch_bytes(rows, d) bytes, 8-B aligned,
+ * = 32 rows fchunks + 4 d rows chunks: the forward's row partials of `fchunks` column chunks and
+ * the backward's gZ partials of `chunks` column chunks, both chosen from (rows, d) alone, the
+ * second held to max(2 rows^2, 3 MiB) bytes (one chunk: none, the backward then writes gZ in
+ * its first launch): O(rows chunks (d + 8)), never rows x rows (0 for arguments out of range).  Z needs 4-B alignment only: rows are read with 16-B loads where d % 4 == 0 and
+ * Z is 16-B aligned and with scalar loads of the same elements otherwise.  2 <= rows <= 65,536,
+ * 1 <= d <= 4,096 (GLL_ERR_UNSUPPORTED past them), V >= 1, rows % V == 0, T and Tb positive and
+ * finite (GLL_ERR_INVALID_ARG).  Stream-ordered, no allocation, no host synchronisation;
+ * argument checks come before any HIP call. */
+#define GLL_SC_ALL 0
+#define GLL_SC_ONE 1
+size_t gll_supcon_scratch_bytes(int64_t rows, int32_t d);
+int gll_supcon_forward(int64_t rows, int32_t V, int32_t d, const float* Z, const int64_t* labels,
+                       int mode, float T, float Tb, double* loss, float* row_loss, float* stats,
+                       void* scratch, void* stream);
+int gll_supcon_backward(int64_t rows, int32_t V, int32_t d, const float* Z, const int64_t* labels,
+                        int mode, float T, float Tb, const float* stats, const double* grad_loss,
+                        float* gZ, void* scratch, void* stream);
+int64_t gll_supcon_launches(void);  /* kernel launches of either call so far in this process (host counter) */
+
 #ifdef __cplusplus
 }
 #endif
