@@ -767,3 +767,109 @@ def stable_conjgrad(A, b, x0=None, max_iter=1e5, tol=1e-10):
         print("max iter reached: ", total, " iters")  # GLL.py:273-274
     out = x.cpu().numpy()
     return out.ravel() if vec else out
+
+
+# ----------------------------------------------------------------------------------------
+# Query-vs-database kNN and the out-of-sample extension (gll_knn_query / gll_extend,
+# DESIGN.md §3.12).  Forward only: no autograd through either.
+# ----------------------------------------------------------------------------------------
+def _check_query(Xq, Xdb, k, what):
+    if not (torch.is_tensor(Xq) and torch.is_tensor(Xdb)):
+        raise TypeError(f"{what}: Xq and Xdb must be tensors")
+    if Xq.dim() != 2 or Xdb.dim() != 2:
+        raise ValueError(f"{what}: Xq must be Q x d and Xdb N x d")
+    N, d = Xdb.shape
+    if Xq.shape[1] != d:
+        raise ValueError(f"{what}: Xq has {Xq.shape[1]} features, Xdb has {d}")
+    if not 1 <= d <= _lib.MAX_D_FEATURES:
+        raise ValueError(f"{what}: d = {d}, need 1 <= d <= {_lib.MAX_D_FEATURES}")
+    if not 1 <= N <= _lib.QUERY_MAX_N:
+        raise ValueError(f"{what}: N = {N}, need 1 <= N <= {_lib.QUERY_MAX_N}")
+    if int(k) != k or not 1 <= k <= min(N, _lib.QUERY_MAX_K):
+        raise ValueError(f"{what}: k = {k} (N = {N}), need 1 <= k <= min(N, {_lib.QUERY_MAX_K})")
+
+
+def _knn_query_device(Xq32, Xdb32, k, flags, status, dev):
+    """gll_knn_query on prepared fp32 device rows: (idx int32 Q x k, d2 float32 Q x k)."""
+    Q, d = Xq32.shape
+    N = Xdb32.shape[0]
+    lib = _lib.lib()
+    nbytes = lib.gll_query_workspace_bytes(Q, N, d, k, flags)
+    if nbytes == 0:
+        raise ValueError(f"unsupported query Q={Q} N={N} d={d} k={k} flags={flags}")
+    idx = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    d2 = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.gll_knn_query(Q, N, d, k, flags, Xq32.data_ptr(), Xdb32.data_ptr(),
+                                 idx.data_ptr(), d2.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                 _stream(dev)), "gll_knn_query")
+    return idx, d2
+
+
+def knn_query(Xq: torch.Tensor, Xdb: torch.Tensor, k: int, flags: int = 0,
+              return_status: bool = False):
+    """idx, d2 = knn_query(Xq, Xdb, k): for every row of Xq (Q x d) the k rows of Xdb (N x d) with
+    the smallest float64 sum_f (q_f - x_f)^2 of the fp32 features, equal distances to the lower
+    index -- exact, like the graph build's kNN.  idx int64 Q x k, d2 float32 Q x k (the fp32
+    difference-form distances), each list ordered by (d2, idx), on Xdb's device.  float16 /
+    bfloat16 / float64 features are converted to float32 first.  flags: _lib.QF_SMALL_PANELS.
+    return_status=True adds the 4 int32 status words of the call (_lib.QST_*, a device tensor)."""
+    _check_query(Xq, Xdb, k, "knn_query")
+    k, flags = int(k), int(flags)
+    if flags & ~_lib.QF_SMALL_PANELS:
+        raise ValueError(f"knn_query: unknown flags {flags}")
+    dev = _device_for(Xdb)
+    with torch.cuda.device(dev):
+        status = torch.zeros(_lib.QST_NWORDS, dtype=torch.int32, device=dev)
+        if Xq.shape[0] == 0:
+            idx = torch.empty((0, k), dtype=torch.int64, device=dev)
+            d2 = torch.empty((0, k), dtype=torch.float32, device=dev)
+        else:
+            idx32, d2 = _knn_query_device(_features(Xq, dev), _features(Xdb, dev), k, flags,
+                                          status, dev)
+            idx = idx32.long()
+    return (idx, d2, status) if return_status else (idx, d2)
+
+
+def extend(Xq: torch.Tensor, Xdb: torch.Tensor, P: torch.Tensor, k: int = DEFAULT_K,
+           epsilon="auto", eps_db=None, return_status: bool = False):
+    """Uq, labels = extend(Xq, Xdb, P, k): the harmonic (Nadaraya-Watson) out-of-sample extension
+    of a solved graph, u(q) = sum_j w_qj P_j / sum_j w_qj over q's k - 1 nearest rows of Xdb
+    (k has the layer's meaning, neighbours including the point itself; a query is not in the
+    database), w = exp(-4 d^2 / (eps_q eps_j)): a fixed epsilon for both, or 'auto': eps_q the
+    distance to the (k - 1)-th nearest and eps_j = eps_db[j] (the database graph's eps, required).
+    P: N x C predictions of the database rows ([Y; U]), read as float32.  Uq float64 Q x C,
+    labels int64 Q (lowest index among the maxima), on Xdb's device."""
+    if not isinstance(k, (int, np.integer)) or not 2 <= k <= MAX_K:
+        raise ValueError(f"extend: k = {k}, need 2 <= k <= {MAX_K} (neighbours incl. self)")
+    _check_query(Xq, Xdb, int(k) - 1, "extend")
+    N = Xdb.shape[0]
+    if not torch.is_tensor(P) or P.dim() != 2 or P.shape[0] != N:
+        raise ValueError(f"extend: P must be N x C with N = {N}")
+    C = P.shape[1]
+    if not 1 <= C <= _lib.QUERY_MAX_C:
+        raise ValueError(f"extend: C = {C}, need 1 <= C <= {_lib.QUERY_MAX_C}")
+    eps = _eps_value(epsilon)
+    if eps == 0.0:
+        if eps_db is None:
+            raise ValueError("extend: epsilon='auto' needs eps_db (the database graph's eps)")
+        if not torch.is_tensor(eps_db) or eps_db.numel() != N:
+            raise ValueError(f"extend: eps_db must hold N = {N} values")
+    kn = int(k) - 1
+    dev = _device_for(Xdb)
+    Q = Xq.shape[0]
+    with torch.cuda.device(dev):
+        status = torch.zeros(_lib.QST_NWORDS, dtype=torch.int32, device=dev)
+        Uq = torch.empty((Q, C), dtype=torch.float64, device=dev)
+        labels = torch.empty(Q, dtype=torch.int64, device=dev)
+        if Q > 0:
+            P32 = P.detach().to(device=dev, dtype=torch.float32).contiguous()
+            e32 = None
+            if eps == 0.0:
+                e32 = eps_db.detach().to(device=dev, dtype=torch.float32).contiguous().view(-1)
+            idx, d2 = _knn_query_device(_features(Xq, dev), _features(Xdb, dev), kn, 0, status, dev)
+            _lib.check(_lib.lib().gll_extend(
+                Q, N, kn, C, idx.data_ptr(), d2.data_ptr(), P32.data_ptr(),
+                None if e32 is None else e32.data_ptr(), ct.c_float(eps), Uq.data_ptr(),
+                labels.data_ptr(), status.data_ptr(), _stream(dev)), "gll_extend")
+    return (Uq, labels, status) if return_status else (Uq, labels)

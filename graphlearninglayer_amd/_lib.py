@@ -54,6 +54,11 @@ SC_ALL, SC_ONE = 0, 1            # gll_supcon_* mode
 SC_TILE, SC_ROWS, SC_KC, SC_TARGET_WG, SC_PART_BYTES, SC_MIN_BUDGET = 32, 64, 128, 512, 32, 3 << 20
 SC_TARGET_WG_FWD = 1024
 SC_MAX_ROWS = 65536
+QF_SMALL_PANELS = 1              # gll_knn_query flag: 64-row panels (tests: the multi-panel path)
+QUERY_MAX_K, QUERY_MAX_C = 256, 256   # gll_knn_query k / gll_extend kn and C
+QUERY_MAX_N = (2**31 - 1) // 2
+QST_RESCAN, QST_NONFINITE, QST_ZERO_SUM = 0, 1, 2   # gll_knn_query / gll_extend status words
+QST_NWORDS = 4
 
 
 def supcon_plan(rows: int, d: int):
@@ -80,6 +85,7 @@ EXPORTS = (
     "gll_features_forward", "gll_features_backward", "gll_features_calls", "gll_fused_plan",
     "gll_objective_head_scratch_bytes", "gll_objective_head_batched",
     "gll_supcon_scratch_bytes", "gll_supcon_forward", "gll_supcon_backward", "gll_supcon_launches",
+    "gll_query_workspace_bytes", "gll_knn_query", "gll_extend", "gll_query_launches",
 )
 
 
@@ -196,6 +202,15 @@ def _declare(lib):
     lib.gll_supcon_backward.restype = i32
     lib.gll_supcon_launches.argtypes = []
     lib.gll_supcon_launches.restype = ct.c_int64
+    i64 = ct.c_int64
+    lib.gll_query_workspace_bytes.argtypes = [i64, i64, ct.c_int32, ct.c_int32, i32]
+    lib.gll_query_workspace_bytes.restype = sz
+    lib.gll_knn_query.argtypes = [i64, i64, ct.c_int32, ct.c_int32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.gll_knn_query.restype = i32
+    lib.gll_extend.argtypes = [i64, i64, ct.c_int32, ct.c_int32, vp, vp, vp, vp, f32, vp, vp, vp, vp]
+    lib.gll_extend.restype = i32
+    lib.gll_query_launches.argtypes = []
+    lib.gll_query_launches.restype = ct.c_int64
     return lib
 
 

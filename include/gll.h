@@ -543,6 +543,50 @@ int gll_supcon_backward(int64_t rows, int32_t V, int32_t d, const float* Z, cons
                         float* gZ, void* scratch, void* stream);
 int64_t gll_supcon_launches(void);  /* kernel launches of either call so far in this process (host counter) */
 
+/* Exact query-vs-database kNN and the out-of-sample extension of a solved graph (query.hip,
+ * DESIGN.md §3.12; no reference counterpart: the reference predicts for new points by rebuilding
+ * and re-solving the whole graph, utils.py:637-660).  Forward only.
+ *
+ * gll_knn_query: for every row q of Xq (Q x d fp32) the k rows of Xdb (N x d fp32) with the
+ * smallest float64 sum_f (q_f - x_f)^2 of the fp32 inputs, equal distances to the lower index --
+ * exact for any finite input, no near-tie allowance.  idx / d2 (Q x k): the list ordered by
+ * (d2, idx), d2 the fp32 difference-form value: feature f on lane (f / 4) % 8 of an 8-lane group,
+ * one fmaf chain a lane in ascending f, then a 3-level tree -- within (4 ceil(d / 32) + 8) 2^-24
+ * relative of the float64 value.  Nominating distances run on the fp32-input MFMA over rows centred
+ * on row 0 of Xdb, |D2 - d^2| <= (d + 16) 2^-24 (|a_q| + |a_j|)^2, a panel of min(Q, cap) query rows
+ * at a time (cap: 128 MiB of panel, a multiple of 64 rows, at least 64; GLL_QF_SMALL_PANELS: 64),
+ * never Q x N; three launches a panel.  status (4 device words, accumulate; the caller zeroes
+ * them): [0] rows that took the exact rescan (certificate failed, or more than 512 columns at the
+ * scan's threshold), diagnostic; [1] rows with a non-finite nominating or returned distance: their
+ * values are unspecified, every index is in [0, N) all the same; [2] gll_extend rows with a zero
+ * or NaN weight sum; [3] unused.  Xq, Xdb need 4-B alignment only (16-B loads where d % 4 == 0
+ * and both are 16-B aligned, scalar loads of the same elements otherwise: the same bits);
+ * workspace: gll_query_workspace_bytes bytes, 16-B aligned.  A row's result does not depend on
+ * the rows that share the call or the panel; two runs are bitwise equal.
+ * 1 <= k <= N (GLL_ERR_INVALID_ARG), k <= 256, 1 <= d <= 4096, N <= INT32_MAX / 2
+ * (GLL_ERR_UNSUPPORTED), Q >= 1; gll_query_workspace_bytes returns 0 for arguments out of range.
+ *
+ * gll_extend: u(q) = sum_i w_i P[idx[q, i]] / sum_i w_i over the kn listed neighbours, in float64
+ * in list order, w_i = exp(-4 double(d2[q, i]) / (eps_q eps_j)): eps > 0: eps_q = eps_j = eps;
+ * eps <= 0 ('auto'): eps_q = sqrtf(d2[q, kn - 1]) (the list's last entry: what GLL.py:205 gives a
+ * point with these neighbours) and eps_j = eps_db[j].  IEEE as written (no clamps): a zero or NaN
+ * weight sum gives a NaN row, counted in status[2]; an index outside [0, N) is not followed and
+ * gives a NaN weight.  label: the margin head's rule -- lowest index among the maxima, NaN after
+ * every number.  One launch.  1 <= kn <= 256, 1 <= C <= 256.
+ * Both calls are stream-ordered, allocate nothing, do not synchronise the host and check their
+ * arguments before any HIP call. */
+#define GLL_QF_SMALL_PANELS 1
+size_t gll_query_workspace_bytes(int64_t Q, int64_t N, int32_t d, int32_t k, int flags);
+int gll_knn_query(int64_t Q, int64_t N, int32_t d, int32_t k, int flags,
+                  const float* Xq, const float* Xdb,
+                  int32_t* idx /*Q x k*/, float* d2 /*Q x k*/,
+                  int32_t* status /*4 words, accumulate*/, void* workspace, void* stream);
+int gll_extend(int64_t Q, int64_t N, int32_t kn, int32_t C,
+               const int32_t* idx, const float* d2 /*Q x kn*/,
+               const float* P /*N x C*/, const float* eps_db /*N, or NULL*/, float eps /*>0, or <=0: auto*/,
+               double* Uq /*Q x C*/, int64_t* label /*Q*/, int32_t* status, void* stream);
+int64_t gll_query_launches(void);  /* kernel launches of either call so far in this process (host counter) */
+
 #ifdef __cplusplus
 }
 #endif
