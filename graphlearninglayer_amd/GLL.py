@@ -771,7 +771,8 @@ def stable_conjgrad(A, b, x0=None, max_iter=1e5, tol=1e-10):
 
 # ----------------------------------------------------------------------------------------
 # Query-vs-database kNN and the out-of-sample extension (gll_knn_query / gll_extend,
-# DESIGN.md §3.12).  Forward only: no autograd through either.
+# DESIGN.md §3.12).  knn_query has no gradient (the lists are frozen); extend is differentiable
+# in Xq, Xdb, P and a fixed epsilon given as a tensor (gll_extend_backward).
 # ----------------------------------------------------------------------------------------
 def _check_query(Xq, Xdb, k, what):
     if not (torch.is_tensor(Xq) and torch.is_tensor(Xdb)):
@@ -839,7 +840,11 @@ def extend(Xq: torch.Tensor, Xdb: torch.Tensor, P: torch.Tensor, k: int = DEFAUL
     database), w = exp(-4 d^2 / (eps_q eps_j)): a fixed epsilon for both, or 'auto': eps_q the
     distance to the (k - 1)-th nearest and eps_j = eps_db[j] (the database graph's eps, required).
     P: N x C predictions of the database rows ([Y; U]), read as float32.  Uq float64 Q x C,
-    labels int64 Q (lowest index among the maxima), on Xdb's device."""
+    labels int64 Q (lowest index among the maxima), on Xdb's device.
+    Differentiable: with grad mode on and Xq, Xdb, P or a one-element tensor epsilon requiring
+    grad, Uq carries a grad_fn (gll_extend_backward: the neighbour lists frozen, as the layer's
+    graph is; gradients in each input's dtype).  eps_db is a constant of the fitted graph and
+    never gets a gradient; labels are not differentiable."""
     if not isinstance(k, (int, np.integer)) or not 2 <= k <= MAX_K:
         raise ValueError(f"extend: k = {k}, need 2 <= k <= {MAX_K} (neighbours incl. self)")
     _check_query(Xq, Xdb, int(k) - 1, "extend")
@@ -858,18 +863,117 @@ def extend(Xq: torch.Tensor, Xdb: torch.Tensor, P: torch.Tensor, k: int = DEFAUL
     kn = int(k) - 1
     dev = _device_for(Xdb)
     Q = Xq.shape[0]
+    eps_t = epsilon if torch.is_tensor(epsilon) else None
+    if Q > 0 and torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad for t in (Xq, Xdb, P, eps_t)):
+        Uq, labels, status = _Extend.apply(Xq, Xdb, P, eps_t, kn, eps, eps_db, dev)
+    else:
+        Uq, labels, status = _extend_forward(Xq, Xdb, P, kn, eps, eps_db, dev)[:3]
+    return (Uq, labels, status) if return_status else (Uq, labels)
+
+
+def _extend_forward(Xq, Xdb, P, kn, eps, eps_db, dev):
+    """gll_knn_query + gll_extend: (Uq, labels, status) and what the backward reads."""
+    Q, N, C = Xq.shape[0], Xdb.shape[0], P.shape[1]
     with torch.cuda.device(dev):
         status = torch.zeros(_lib.QST_NWORDS, dtype=torch.int32, device=dev)
         Uq = torch.empty((Q, C), dtype=torch.float64, device=dev)
         labels = torch.empty(Q, dtype=torch.int64, device=dev)
+        saved = None
         if Q > 0:
             P32 = P.detach().to(device=dev, dtype=torch.float32).contiguous()
             e32 = None
             if eps == 0.0:
                 e32 = eps_db.detach().to(device=dev, dtype=torch.float32).contiguous().view(-1)
-            idx, d2 = _knn_query_device(_features(Xq, dev), _features(Xdb, dev), kn, 0, status, dev)
+            Xq32, Xdb32 = _features(Xq, dev), _features(Xdb, dev)
+            idx, d2 = _knn_query_device(Xq32, Xdb32, kn, 0, status, dev)
             _lib.check(_lib.lib().gll_extend(
                 Q, N, kn, C, idx.data_ptr(), d2.data_ptr(), P32.data_ptr(),
                 None if e32 is None else e32.data_ptr(), ct.c_float(eps), Uq.data_ptr(),
                 labels.data_ptr(), status.data_ptr(), _stream(dev)), "gll_extend")
-    return (Uq, labels, status) if return_status else (Uq, labels)
+            saved = (Xq32, Xdb32, idx, d2, P32, e32)
+    return Uq, labels, status, saved
+
+
+def _extend_backward_device(Xq32, Xdb32, idx, d2, P32, e32, eps, gU, what, flags=0):
+    """gll_extend_backward on prepared device arrays: (gXq, gXdb, gP fp32, grad_eps float64 --
+    None where not selected -- and the call's 4 status words)."""
+    Q, d = Xq32.shape
+    N, C = P32.shape
+    kn = idx.shape[1]
+    dev = Xdb32.device
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        nbytes = lib.gll_extend_grad_workspace_bytes(Q, N, kn, d, C, what, flags)
+        if nbytes == 0:
+            raise ValueError(f"unsupported extend backward Q={Q} N={N} kn={kn} d={d} C={C} "
+                             f"what={what} flags={flags}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        status = torch.zeros(_lib.QST_NWORDS, dtype=torch.int32, device=dev)
+        gXq = torch.empty((Q, d), dtype=torch.float32, device=dev) if what & _lib.EG_XQ else None
+        gXdb = torch.empty((N, d), dtype=torch.float32, device=dev) if what & _lib.EG_XDB else None
+        gP = torch.empty((N, C), dtype=torch.float32, device=dev) if what & _lib.EG_P else None
+        geps = torch.empty(1, dtype=torch.float64, device=dev) if what & _lib.EG_EPS else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(lib.gll_extend_backward(
+            Q, N, kn, d, C, Xq32.data_ptr(), Xdb32.data_ptr(), idx.data_ptr(), d2.data_ptr(),
+            P32.data_ptr(), ptr(e32), ct.c_float(eps), gU.data_ptr(), what, flags, ptr(gXq),
+            ptr(gXdb), ptr(gP), ptr(geps), status.data_ptr(), ws.data_ptr(), _stream(dev)),
+            "gll_extend_backward")
+    return gXq, gXdb, gP, geps, status
+
+
+class _Extend(torch.autograd.Function):
+    """extend with its hand-written backward (gll_extend_backward): the neighbour
+    lists are frozen, eps_db is a constant, labels and status carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, Xq, Xdb, P, eps_t, kn, eps, eps_db, dev):
+        Uq, labels, status, saved = _extend_forward(Xq, Xdb, P, kn, eps, eps_db, dev)
+        ctx.save_for_backward(*saved)   # (Uq is recomputed by the kernel, bit for bit)
+        ctx.eps = eps
+        ctx.like = tuple(None if t is None else (t.dtype, t.device, t.shape)
+                         for t in (Xq, Xdb, P, eps_t))
+        ctx.mark_non_differentiable(labels, status)
+        return Uq, labels, status
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gU, *_):
+        Xq32, Xdb32, idx, d2, P32, e32 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        what = ((_lib.EG_XQ if need[0] else 0) | (_lib.EG_XDB if need[1] else 0) |
+                (_lib.EG_P if need[2] else 0) | (_lib.EG_EPS if need[3] else 0))
+        if what == 0:
+            return (None,) * 8
+        dev = Xdb32.device
+        with torch.cuda.device(dev):
+            g64 = gU.detach().to(device=dev, dtype=torch.float64).contiguous()
+            outs = _extend_backward_device(Xq32, Xdb32, idx, d2, P32, e32, ctx.eps, g64, what)[:4]
+
+        def back(g, like):
+            if g is None:
+                return None
+            dtype, device, shape = like
+            return g.to(device=device, dtype=dtype).reshape(shape)
+
+        return tuple(back(g, like) for g, like in zip(outs, ctx.like)) + (None,) * 4
+
+
+def extend_torch(Xq, Xdb, P, idx, epsilon="auto", eps_db=None):
+    """The extension's formula in plain PyTorch on given neighbour lists idx (Q x kn, nearest
+    first): Uq = sum_i w_i P[idx_i] / sum_i w_i, w_i = exp(-4 d_i^2 / (eps_q eps_j)), d_i^2 =
+    sum_f (q_f - x_f)^2, eps_q = d_(kn-1) and eps_j = eps_db[j] for 'auto'.  Everything in the
+    inputs' dtype and differentiable by autograd: the yardstick of extend and its backward (as
+    cw_margin and supcon_loss_torch are for theirs), not a code path of the package."""
+    idx = idx.long()
+    diff = Xq[:, None, :] - Xdb[idx]
+    d2 = (diff * diff).sum(-1)
+    if isinstance(epsilon, str):
+        if epsilon != "auto":
+            raise ValueError(f"epsilon must be a number or 'auto', got {epsilon!r}")
+        den = d2[:, -1:].sqrt() * eps_db.to(d2.dtype).view(-1)[idx]
+    else:
+        den = epsilon * epsilon
+    w = torch.exp(-4.0 * d2 / den)
+    return (w[:, :, None] * P[idx]).sum(1) / w.sum(1, keepdim=True)

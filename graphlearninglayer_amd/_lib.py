@@ -59,6 +59,9 @@ QUERY_MAX_K, QUERY_MAX_C = 256, 256   # gll_knn_query k / gll_extend kn and C
 QUERY_MAX_N = (2**31 - 1) // 2
 QST_RESCAN, QST_NONFINITE, QST_ZERO_SUM = 0, 1, 2   # gll_knn_query / gll_extend status words
 QST_NWORDS = 4
+EG_XQ, EG_XDB, EG_P, EG_EPS = 1, 2, 4, 8   # gll_extend_backward `what` bits
+EGF_SMALL_LISTS = 1              # gll_extend_backward flag: 64-entry in-LDS lists (tests: the long-list path)
+EGST_ZERO_SUM, EGST_LONG_LIST = 2, 3   # gll_extend_backward status words
 
 
 def supcon_plan(rows: int, d: int):
@@ -86,6 +89,7 @@ EXPORTS = (
     "gll_objective_head_scratch_bytes", "gll_objective_head_batched",
     "gll_supcon_scratch_bytes", "gll_supcon_forward", "gll_supcon_backward", "gll_supcon_launches",
     "gll_query_workspace_bytes", "gll_knn_query", "gll_extend", "gll_query_launches",
+    "gll_extend_grad_workspace_bytes", "gll_extend_backward", "gll_extend_grad_launches",
 )
 
 
@@ -211,6 +215,14 @@ def _declare(lib):
     lib.gll_extend.restype = i32
     lib.gll_query_launches.argtypes = []
     lib.gll_query_launches.restype = ct.c_int64
+    i32s = ct.c_int32
+    lib.gll_extend_grad_workspace_bytes.argtypes = [i64, i64, i32s, i32s, i32s, i32, i32]
+    lib.gll_extend_grad_workspace_bytes.restype = sz
+    lib.gll_extend_backward.argtypes = [i64, i64, i32s, i32s, i32s, vp, vp, vp, vp, vp, vp, f32, vp,
+                                        i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.gll_extend_backward.restype = i32
+    lib.gll_extend_grad_launches.argtypes = []
+    lib.gll_extend_grad_launches.restype = ct.c_int64
     return lib
 
 

@@ -107,7 +107,9 @@ def laplace_fit(X, train_labels, knn_num=50, epsilon="auto", n_classes="auto", t
 def laplace_predict(fit, Xq, knn_num=50, epsilon=None):
     """(Uq float64 Q x C, labels int64 Q) for new points from a laplace_fit, by the harmonic
     extension over their knn_num - 1 nearest fitted points (GLL.extend): no new graph, no solve.
-    epsilon: the fit's by default."""
+    epsilon: the fit's by default.  Differentiable as GLL.extend is: Uq carries a grad_fn when Xq
+    (a tensor) requires grad, or fit.X / fit.P if the caller made them require grad; the fit's
+    eps gets no gradient."""
     Xt = Xq if torch.is_tensor(Xq) else torch.from_numpy(np.ascontiguousarray(Xq))
     return GLL.extend(Xt, fit.X, fit.P, k=knn_num,
                       epsilon=fit.epsilon if epsilon is None else epsilon, eps_db=fit.eps)

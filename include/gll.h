@@ -545,7 +545,8 @@ int64_t gll_supcon_launches(void);  /* kernel launches of either call so far in 
 
 /* Exact query-vs-database kNN and the out-of-sample extension of a solved graph (query.hip,
  * DESIGN.md §3.12; no reference counterpart: the reference predicts for new points by rebuilding
- * and re-solving the whole graph, utils.py:637-660).  Forward only.
+ * and re-solving the whole graph, utils.py:637-660).  The extension's backward is
+ * gll_extend_backward below.
  *
  * gll_knn_query: for every row q of Xq (Q x d fp32) the k rows of Xdb (N x d fp32) with the
  * smallest float64 sum_f (q_f - x_f)^2 of the fp32 inputs, equal distances to the lower index --
@@ -586,6 +587,54 @@ int gll_extend(int64_t Q, int64_t N, int32_t kn, int32_t C,
                const float* P /*N x C*/, const float* eps_db /*N, or NULL*/, float eps /*>0, or <=0: auto*/,
                double* Uq /*Q x C*/, int64_t* label /*Q*/, int32_t* status, void* stream);
 int64_t gll_query_launches(void);  /* kernel launches of either call so far in this process (host counter) */
+
+/* Backward of gll_extend (extend_grad.hip).  The neighbour lists are frozen, as
+ * the layer's kNN graph is.  For query q and list entry i, with j = idx[q, i], d_i =
+ * double(d2[q, i]) (the fp32 value gll_knn_query returned), e_q and e_j as in gll_extend,
+ *   t_i = 4 d_i / (e_q e_j),  w_i = exp(-t_i),  S = sum_i w_i,  u = sum_i w_i P[j] / S
+ * and g = gU[q] (float64 Q x C, dL/dUq):
+ *   r_i = sum_c g_c (P[j, c] - u_c)        beta_i = w_i r_i / S        a_i = w_i / S
+ *   c_i = -4 beta_i / (e_q e_j)            'auto': c_(kn-1) += (sum_i beta_i t_i) / (2 d_(kn-1))
+ *   gXq[q]   =  2 sum_i c_i (x_q - x_j)
+ *   gXdb[j]  = -2 sum_{(q, i): idx[q, i] = j} c_i (x_q - x_j)
+ *   gP[j, c] =    sum_{(q, i): idx[q, i] = j} a_i g[q, c]
+ *   grad_eps =    sum_q sum_i 2 beta_i t_i / eps                          fixed eps only
+ * eps_db is a constant of the fitted graph: it gets no gradient.  The differences x_q - x_j are
+ * exact in float64; every product and sum is float64, rounded to nearest, in a fixed order (list
+ * order within a query row, ascending query within a database row, ascending row for grad_eps);
+ * u is recomputed with gll_extend's operations, so it has gll_extend's bits; each output is
+ * rounded once to fp32 (grad_eps stays float64).  No floating-point atomics: two runs are bitwise
+ * equal, gXq[q] does not depend on the other rows of the call, and the bits do not depend on
+ * `what`, `flags` or the alignment.  IEEE as written (no clamps): a row whose weight sum is zero
+ * or NaN has a NaN gXq row and makes the database rows it lists NaN (and grad_eps), every other
+ * row is unaffected.  An index outside [0, N) is not followed: the entry contributes to no
+ * database row and its query row's gradients are NaN.
+ * `what`: GLL_EG_* bits, at least one; gXq: Q x d, gXdb: N x d, gP: N x C fp32, grad_eps: one
+ * float64; an output not selected may be NULL.  GLL_EG_EPS with eps <= 0 ('auto') is
+ * GLL_ERR_INVALID_ARG.  status (4 device words, accumulate, the caller zeroes them): [2] query
+ * rows with a zero or NaN weight sum; [3] database rows whose list did not fit the in-LDS
+ * capacity (512 entries; GLL_EGF_SMALL_LISTS: 64) and was ordered in global memory, diagnostic;
+ * [0], [1] unused.  workspace: gll_extend_grad_workspace_bytes bytes, 16-B aligned (0 for
+ * arguments out of range).  Launches: 1 (the row kernel) + 4 when GLL_EG_XDB or GLL_EG_P is
+ * selected (count, scan, fill, database rows) + 1 with GLL_EG_EPS; counted by
+ * gll_extend_grad_launches alone.  Xq, Xdb need 4-B alignment only (16-B loads where d % 4 == 0
+ * and both are 16-B aligned, scalar loads of the same elements otherwise).  1 <= kn, C <= 256,
+ * 1 <= d <= 4096, N, Q <= INT32_MAX / 2 (GLL_ERR_UNSUPPORTED past them).  Stream-ordered, no
+ * allocation, no host synchronisation; argument checks come before any HIP call. */
+#define GLL_EG_XQ 1
+#define GLL_EG_XDB 2
+#define GLL_EG_P 4
+#define GLL_EG_EPS 8
+#define GLL_EGF_SMALL_LISTS 1   /* tests: shrink the in-LDS list capacity to 64 entries */
+size_t gll_extend_grad_workspace_bytes(int64_t Q, int64_t N, int32_t kn, int32_t d, int32_t C,
+                                       int what, int flags);
+int gll_extend_backward(int64_t Q, int64_t N, int32_t kn, int32_t d, int32_t C,
+                        const float* Xq, const float* Xdb, const int32_t* idx, const float* d2,
+                        const float* P, const float* eps_db, float eps, const double* gU,
+                        int what, int flags,
+                        float* gXq, float* gXdb, float* gP, double* grad_eps,
+                        int32_t* status, void* workspace, void* stream);
+int64_t gll_extend_grad_launches(void);  /* kernel launches of gll_extend_backward so far in this process (host counter) */
 
 #ifdef __cplusplus
 }
