@@ -40,7 +40,14 @@ Deliberate differences from the reference (all documented in DESIGN.md):
     with F.normalize(feat, dim=1) in its last line (networks/BuildNet.py:101) -- and float16 /
     bfloat16 features are read as they are: one launch in front of the graph build, one behind
     its backward, the gradient in X's dtype (gll_features_forward / _backward, DESIGN.md §3.8;
-    unit_features / unit_features_backward are the two stages on their own).
+    unit_features / unit_features_backward are the two stages on their own);
+  * an optional last argument `neighbors` of apply / ce_loss / margin_loss / objective (and of
+    device_graph, utils.laplace, utils.laplace_fit, utils.gl_accuracy) gives the neighbour lists
+    instead of the search: an integer tensor n x k (the reference's knn_ind, GLL.py:186, column
+    0 = self and not read) or n x (k - 1), in the caller's order, which is kept -- the last
+    column is knn_ind[:, -1] of GLL.py:205.  The graph is built from them with exact distances
+    and no n x n buffer (gll_forward_lists_batched); the lists are frozen, as
+    the searched graph is.
 """
 from __future__ import annotations
 
@@ -108,6 +115,9 @@ def _warn_from(st):
                       "instead: correct, slower", RuntimeWarning)
     if st[_lib.ST_TINY_EPS]:
         warnings.warn("Epsilon in KNN is very close to zero.", UserWarning)  # GLL.py:240-241
+    if st[_lib.ST_LIST_DROPPED]:
+        warnings.warn(f"GLL neighbors: {st[_lib.ST_LIST_DROPPED]} list entries were dropped (an "
+                      "index outside [0, n) or a repeat within a row)", UserWarning)
     if st[_lib.ST_FWD_NONCONV]:
         warnings.warn(f"GLL forward CG: {st[_lib.ST_FWD_NONCONV]} column solve(s) reached "
                       f"max_iter ({st[_lib.ST_FWD_ITERS]} iterations)", RuntimeWarning)
@@ -185,6 +195,31 @@ def _eps_value(epsilon) -> float:
     return e
 
 
+def _check_neighbors(neighbors, lead, n, k):
+    """The caller's neighbour lists: an integer tensor lead x n x K (column 0, the self column,
+    is not read) or lead x n x (K - 1), K = min(k, n).  Metadata alone: no GPU call, no host
+    sync."""
+    K = min(int(k), int(n))
+    if not torch.is_tensor(neighbors):
+        raise TypeError("neighbors must be a Tensor")
+    if neighbors.is_floating_point() or neighbors.is_complex() or neighbors.dtype == torch.bool:
+        raise ValueError("neighbors must hold integers (int32 or int64)")
+    want = tuple(lead) + (n,)
+    if neighbors.dim() != len(want) + 1 or tuple(neighbors.shape[:-1]) != want \
+            or neighbors.shape[-1] not in (K, K - 1):
+        raise ValueError(f"neighbors must be {'B x ' if lead else ''}n x k or n x (k - 1) = "
+                         f"{n} x {K} or {K - 1}")
+
+
+def _neighbors_arg(neighbors, lead, n, k, dev):
+    """The lists as the C ABI takes them: int32, contiguous, on `dev`, lead x n x (K - 1)."""
+    _check_neighbors(neighbors, lead, n, k)
+    nb = neighbors.detach()
+    if nb.shape[-1] == min(int(k), int(n)):
+        nb = nb[..., 1:]
+    return nb.to(device=dev, dtype=torch.int32).contiguous()
+
+
 def make_problem(n, d, base, C, k=DEFAULT_K, tau=0.0, epsilon="auto",
                  rtol=DEFAULT_RTOL, max_iter=DEFAULT_MAX_ITER, flags=0) -> _lib.Problem:
     return _lib.Problem(n=int(n), d=int(d), base=int(base), C=int(C), K=int(min(k, n)),
@@ -212,10 +247,10 @@ class LaplaceLearningSparseHard(torch.autograd.Function):
     apply = staticmethod(_ext_mod.apply)
 
     @classmethod
-    def apply_python(cls, X, label_matrix, tau=0, epsilon="auto", k=DEFAULT_K):
+    def apply_python(cls, X, label_matrix, tau=0, epsilon="auto", k=DEFAULT_K, neighbors=None):
         """The Python torch.autograd.Function path (ctypes onto the same C ABI)."""
         _check_k(k, X.shape[-2])
-        return super().apply(X, label_matrix, tau, epsilon, k)
+        return super().apply(X, label_matrix, tau, epsilon, k, neighbors)
 
     ce_loss = staticmethod(_ext_mod.ce_loss)
 
@@ -250,23 +285,25 @@ class LaplaceLearningSparseHard(torch.autograd.Function):
                                       score, score_out, indices)
 
     @staticmethod
-    def forward(ctx, X, label_matrix, tau=0, epsilon="auto", k=DEFAULT_K):
-        U = _layer_forward(ctx, X, label_matrix, tau, epsilon, k)
+    def forward(ctx, X, label_matrix, tau=0, epsilon="auto", k=DEFAULT_K, neighbors=None):
+        U = _layer_forward(ctx, X, label_matrix, tau, epsilon, k, neighbors)
         return U if X.is_cuda else U.cpu()
 
     @staticmethod
     def backward(ctx, grad_output):
-        return (*_layer_backward(ctx, grad_output, ctx.needs_input_grad), None)
+        return (*_layer_backward(ctx, grad_output, ctx.needs_input_grad), None, None)
 
 
-def _layer_forward(ctx, X, label_matrix, tau, epsilon, k):
+def _layer_forward(ctx, X, label_matrix, tau, epsilon, k, neighbors=None):
     """The forward of the Python path; returns U on the device and leaves the state of
     _layer_backward on ctx."""
-    dev = _device_for(X)
-    _poll_status(dev)
     if X.dim() not in (2, 3) or label_matrix.dim() not in (2, X.dim()):
         raise ValueError("X must be n x d (or B x n x d), label_matrix base x C "
                          "(or B x base x C)")
+    if neighbors is not None:
+        _check_neighbors(neighbors, X.shape[:-2], X.shape[-2], k)
+    dev = _device_for(X)
+    _poll_status(dev)
     B = X.shape[0] if X.dim() == 3 else 1
     n, d = X.shape[-2:]
     base, C = label_matrix.shape[-2:]
@@ -277,17 +314,26 @@ def _layer_forward(ctx, X, label_matrix, tau, epsilon, k):
             Y = Y.unsqueeze(0).expand(B, base, C).contiguous()   # shared labels
         if X.dim() == 3 and Y.shape[0] != B:
             raise ValueError(f"label_matrix batch {Y.shape[0]} != {B}")
-        prob = make_problem(n, d, base, C, k, tau, epsilon)
+        nb = None if neighbors is None else _neighbors_arg(neighbors, X.shape[:-2], n, k, dev)
+        prob = make_problem(n, d, base, C, k, tau, epsilon,
+                            flags=0 if nb is None else _lib.FLAG_KNN_GIVEN)
         prob.status_sink = _ext_mod.status_sink(dev.index)
         nbytes = _lib.lib().gll_workspace_bytes(ct.byref(prob))
         if nbytes == 0:
             raise ValueError(f"unsupported GLL problem n={n} d={d} base={base} C={C} k={k}")
         ws = torch.empty(nbytes * B, dtype=torch.uint8, device=dev)
         U = torch.empty(X.shape[:-2] + (n - base, C), dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib().gll_forward_batched(ct.byref(prob), B, X32.data_ptr(),
-                                                  Y.data_ptr(), ydt, ws.data_ptr(),
-                                                  U.data_ptr(), _stream(dev)),
-                   "gll_forward")
+        if nb is None:
+            _lib.check(_lib.lib().gll_forward_batched(ct.byref(prob), B, X32.data_ptr(),
+                                                      Y.data_ptr(), ydt, ws.data_ptr(),
+                                                      U.data_ptr(), _stream(dev)),
+                       "gll_forward")
+        else:
+            _lib.check(_lib.lib().gll_forward_lists_batched(ct.byref(prob), B, X32.data_ptr(),
+                                                            nb.data_ptr(), Y.data_ptr(), ydt,
+                                                            ws.data_ptr(), U.data_ptr(),
+                                                            _stream(dev)),
+                       "gll_forward_lists")
         _ext_mod.note_call(dev.index)
     ctx.save_for_backward(X)
     ctx.prob, ctx.ws, ctx.dev, ctx.B = prob, ws, dev, B
@@ -616,22 +662,33 @@ def custom_ce_loss(pred, targets):
 # ----------------------------------------------------------------------------------------
 # knn_sym_dist: device graph, returned as the reference's scipy objects
 # ----------------------------------------------------------------------------------------
-def device_graph(X: torch.Tensor, k: int = DEFAULT_K, epsilon="auto", flags: int = 0):
+def device_graph(X: torch.Tensor, k: int = DEFAULT_K, epsilon="auto", flags: int = 0,
+                 neighbors=None):
     """Build the symmetric kNN graph on the GPU; returns a dict of device tensors
     (knn_idx, knn_d2, eps, row_ptr, col, w, d2, deg).  `flags`: gll_problem.flags
-    (e.g. _lib.FLAG_KNN_PANEL, row panels instead of the n x n distances)."""
+    (e.g. _lib.FLAG_KNN_PANEL, row panels instead of the n x n distances).  `neighbors`: the
+    caller's lists (n x k or n x (k - 1) integers) instead of the search -- no n x n buffer;
+    knn_idx then holds them in the caller's order (dropped entries padded with the row itself)."""
     _check_k(k, X.shape[0])
+    if neighbors is not None:
+        _check_neighbors(neighbors, (), X.shape[0], k)
     dev = _device_for(X)
     n, d = X.shape
     with torch.cuda.device(dev):
         X32 = _features(X, dev)
-        prob = make_problem(n, d, 0, 1, k, 0.0, epsilon, flags=flags)
+        nb = None if neighbors is None else _neighbors_arg(neighbors, (), n, k, dev)
+        prob = make_problem(n, d, 0, 1, k, 0.0, epsilon,
+                            flags=flags | (0 if nb is None else _lib.FLAG_KNN_GIVEN))
         nbytes = _lib.lib().gll_workspace_bytes(ct.byref(prob))
         if nbytes == 0:
             raise ValueError(f"unsupported graph problem n={n} d={d} k={k}")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _lib.check(_lib.lib().gll_graph(ct.byref(prob), X32.data_ptr(), ws.data_ptr(),
-                                        _stream(dev)), "gll_graph")
+        if nb is None:
+            _lib.check(_lib.lib().gll_graph(ct.byref(prob), X32.data_ptr(), ws.data_ptr(),
+                                            _stream(dev)), "gll_graph")
+        else:
+            _lib.check(_lib.lib().gll_graph_lists(ct.byref(prob), X32.data_ptr(), nb.data_ptr(),
+                                                  ws.data_ptr(), _stream(dev)), "gll_graph_lists")
         view = _lib.View()
         _lib.check(_lib.lib().gll_workspace_view(ct.byref(prob), ws.data_ptr(), ct.byref(view)),
                    "gll_workspace_view")

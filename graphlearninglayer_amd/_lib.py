@@ -28,6 +28,7 @@ FLAG_BWD_UNFUSED = 16384  # adjoint CG and gradient as two launches
 FLAG_KNN_PANEL = 65536    # kNN in row panels (O(panel x n) distances)
 FLAG_D2_F32 = 131072      # fp32 distance matrix on the pre-split Gram route
 FLAG_ROW_ORDER_OFF = 262144   # large single graphs: row-index order instead of the locality order
+FLAG_KNN_GIVEN = 524288   # caller-supplied neighbour lists (gll_forward_lists_batched): no n x n buffer
 # process-wide test knobs (gll_set_knob): force a code path, 0 = automatic
 KNOB_VR_RV, KNOB_GRID_CAP, KNOB_GRAM_TILE, KNOB_SEL_FORM, KNOB_GRAM_TAIL, KNOB_ROW_PRE = 0, 1, 2, 3, 4, 5
 KNOB_GRAD_SPLIT = 6   # fused backward: long rows in feature parts (0 automatic, 1 on, 2 off)
@@ -37,6 +38,7 @@ ST_SOLVE_FAILED = 6   # the fused backward gave up on its adjoint solves: grad N
 ST_GRID_RESCUED = 10  # whole-GPU CG solves rescued by one workgroup after a lost grid barrier
 ST_KNN_MERGE = 7   # kNN rows that took the full-row select fallback (diagnostic)
 ST_GRAD_SPLIT = 12  # rows the last fused backward ran as 2 or 4 waves over feature parts (diagnostic)
+ST_LIST_DROPPED = 13  # caller-supplied list entries dropped as out of range or repeated (count)
 ST_NWORDS = 16
 K_GRAM, K_SELECT, K_FINALIZE, K_CG, K_EDGE, K_GRAD = range(6)
 K_BWD = 6     # cg_grad_fused_kernel
@@ -90,6 +92,7 @@ EXPORTS = (
     "gll_supcon_scratch_bytes", "gll_supcon_forward", "gll_supcon_backward", "gll_supcon_launches",
     "gll_query_workspace_bytes", "gll_knn_query", "gll_extend", "gll_query_launches",
     "gll_extend_grad_workspace_bytes", "gll_extend_backward", "gll_extend_grad_launches",
+    "gll_forward_lists_batched", "gll_graph_lists",
 )
 
 
@@ -223,6 +226,10 @@ def _declare(lib):
     lib.gll_extend_backward.restype = i32
     lib.gll_extend_grad_launches.argtypes = []
     lib.gll_extend_grad_launches.restype = ct.c_int64
+    lib.gll_forward_lists_batched.argtypes = [P, i32, vp, vp, vp, i32, vp, vp, vp]
+    lib.gll_forward_lists_batched.restype = i32
+    lib.gll_graph_lists.argtypes = [P, vp, vp, vp, vp]
+    lib.gll_graph_lists.restype = i32
     return lib
 
 

@@ -1,6 +1,6 @@
 // api.hip -- the extern "C" boundary declared in include/gll.h.
 //
-// Orchestrates the kernels of gram.hip, select.hip, order.hip, rows.hip, solve.hip / gridcg.hip,
+// Orchestrates the kernels of gram.hip, select.hip, order.hip, ingest.hip, rows.hip, solve.hip / gridcg.hip,
 // grad.hip, param_grad.hip, loss.hip and features.hip on the caller's stream.  No allocation, no host synchronisation: the caller owns the workspace (the
 // Python mirror takes it from torch's caching allocator) and keeps it alive from
 // gll_forward to gll_backward, as the reference keeps its graph on ctx (GLL.py:69-70).
@@ -167,6 +167,11 @@ static int check(const gll_problem* p) {
     const int K = p->K < p->n ? p->K : p->n;
     if (K - 1 > kMaxKm1Huge) return GLL_ERR_UNSUPPORTED;  // the wide select's LDS lists
     if (p->flags & ~GLL_FLAG_ALL) return GLL_ERR_INVALID_ARG;   // unknown (or retired) flags
+    // caller-supplied lists: no search to steer
+    if ((p->flags & GLL_FLAG_KNN_GIVEN) &&
+        (p->flags & (GLL_FLAG_KNN_PANEL | GLL_FLAG_GRAM_INLINE | GLL_FLAG_D2_F32 |
+                     GLL_FLAG_ROW_ORDER_OFF)))
+        return GLL_ERR_INVALID_ARG;
     if (p->C > 256) return GLL_ERR_UNSUPPORTED;       // rhs accumulators per lane
     if ((p->d + 255) / 256 > 16) return GLL_ERR_UNSUPPORTED;  // d <= 4096 in the SpMM
     if (int64_t(p->n) * K > INT32_MAX / 2) return GLL_ERR_UNSUPPORTED;
@@ -224,18 +229,34 @@ static int build_graph(const gll_problem* p, const Layout& L, const Batch& bt, c
     return hip_status(launch_finalize(L, bt, ws, Y, y_dtype, p->tau, auto_eps ? 0.f : p->eps, s));
 }
 
+// The same from caller-supplied lists: reset + ingest (ingest.hip) -> row build
+static int build_graph_lists(const gll_problem* p, const Layout& L, const Batch& bt, const float* X,
+                             const int32_t* nbr, const void* Y, int y_dtype, void* ws,
+                             hipStream_t s) {
+    const bool auto_eps = !(p->eps > 0.f);
+    if (launch_ingest(L, bt, ws, X, nbr, p->eps, auto_eps, vec_ok(X, p->d),
+                      public_status(p, L, ws), s) != hipSuccess)
+        return GLL_ERR_HIP;
+    return hip_status(launch_finalize(L, bt, ws, Y, y_dtype, p->tau, auto_eps ? 0.f : p->eps, s));
+}
+
+// nbr: NULL on the searched route (which refuses GLL_FLAG_KNN_GIVEN); the lists route requires both
 static int forward_impl(const gll_problem* p, int B, const float* X, const void* Y, int y_dtype,
-                        void* ws, double* U, void* stream) {
+                        void* ws, double* U, void* stream, const int32_t* nbr = nullptr,
+                        bool lists = false) {
     int rc = check(p);
     if (rc != GLL_OK) return rc;
     if (B < 1 || B > 65535) return GLL_ERR_INVALID_ARG;
+    if (lists != ((p->flags & GLL_FLAG_KNN_GIVEN) != 0) || (lists && !nbr))
+        return GLL_ERR_INVALID_ARG;
     if (!X || !ws || (p->base > 0 && !Y) || (p->n > p->base && !U)) return GLL_ERR_INVALID_ARG;
     if (y_dtype != GLL_DT_F32 && y_dtype != GLL_DT_F64 && y_dtype != GLL_DT_I64)
         return GLL_ERR_INVALID_ARG;
     Layout L(*p);
     const Batch bt = make_batch(p, L, B, y_dtype, GLL_DT_F32);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = build_graph(p, L, bt, X, Y, y_dtype, ws, s);
+    rc = lists ? build_graph_lists(p, L, bt, X, nbr, Y, y_dtype, ws, s)
+               : build_graph(p, L, bt, X, Y, y_dtype, ws, s);
     if (rc != GLL_OK) return rc;
     const float rtol = p->rtol > 0.f ? p->rtol : 1e-6f;
     const int max_iter = p->max_iter > 0 ? p->max_iter : 1000;
@@ -293,10 +314,28 @@ int gll_graph(const gll_problem* p, const float* X, void* ws, void* stream) {
     if (rc != GLL_OK) return rc;
     if (!X || !ws) return GLL_ERR_INVALID_ARG;
     if (p->base != 0) return GLL_ERR_INVALID_ARG;  // graph only: no labeled block
+    if (p->flags & GLL_FLAG_KNN_GIVEN) return GLL_ERR_INVALID_ARG;   // gll_graph_lists
     Layout L(*p);
     // base = 0: every row is "unlabeled", rhs = 0 and no label is read
     return build_graph(p, L, make_batch(p, L, 1, GLL_DT_F32, GLL_DT_F32), X, nullptr, GLL_DT_F32,
                        ws, static_cast<hipStream_t>(stream));
+}
+
+int gll_graph_lists(const gll_problem* p, const float* X, const int32_t* nbr, void* ws,
+                    void* stream) {
+    int rc = check(p);
+    if (rc != GLL_OK) return rc;
+    if (!(p->flags & GLL_FLAG_KNN_GIVEN) || !nbr) return GLL_ERR_INVALID_ARG;
+    if (!X || !ws) return GLL_ERR_INVALID_ARG;
+    if (p->base != 0) return GLL_ERR_INVALID_ARG;  // graph only: no labeled block
+    Layout L(*p);
+    return build_graph_lists(p, L, make_batch(p, L, 1, GLL_DT_F32, GLL_DT_F32), X, nbr, nullptr,
+                             GLL_DT_F32, ws, static_cast<hipStream_t>(stream));
+}
+
+int gll_forward_lists_batched(const gll_problem* p, int B, const float* X, const int32_t* nbr,
+                              const void* Y, int y_dtype, void* ws, double* U, void* stream) {
+    return forward_impl(p, B, X, Y, y_dtype, ws, U, stream, nbr, true);
 }
 
 int gll_forward(const gll_problem* p, const float* X, const void* Y, int y_dtype, void* ws,
@@ -521,6 +560,7 @@ int gll_workspace_knn_view(const gll_problem* p, int B, void* ws, gll_knn_view* 
     int rc = check(p);
     if (rc != GLL_OK) return rc;
     if (B < 1 || B > 65535 || !ws || !out) return GLL_ERR_INVALID_ARG;
+    if (p->flags & GLL_FLAG_KNN_GIVEN) return GLL_ERR_INVALID_ARG;   // no search stage, no arrays
     Layout L(*p);
     if (L.PR < L.n && B > 1) return GLL_ERR_UNSUPPORTED;   // row panels: single graphs
     Batch bt;
@@ -547,6 +587,7 @@ int gll_gram_route(const gll_problem* p, int B, int x_aligned, int cus,
     int rc = check(p);
     if (rc != GLL_OK) return rc;
     if (B < 1 || B > 65535 || cus < 1 || !out) return GLL_ERR_INVALID_ARG;
+    if (p->flags & GLL_FLAG_KNN_GIVEN) return GLL_ERR_INVALID_ARG;   // no Gram
     Layout L(*p);
     if (L.PR < L.n && B > 1) return GLL_ERR_UNSUPPORTED;   // row panels: single graphs
     Batch bt;
@@ -631,6 +672,7 @@ int gll_select_route(const gll_problem* p, int B, int x_aligned, int rows,
     int rc = check(p);
     if (rc != GLL_OK) return rc;
     if (B < 1 || B > 65535 || !out) return GLL_ERR_INVALID_ARG;
+    if (p->flags & GLL_FLAG_KNN_GIVEN) return GLL_ERR_INVALID_ARG;   // no select
     Layout L(*p);
     // rows: a panel of the problem's row panels (one graph), or all n
     if (L.PR < L.n ? (B > 1 || rows < 1 || rows > L.PR) : rows != L.n) return GLL_ERR_INVALID_ARG;

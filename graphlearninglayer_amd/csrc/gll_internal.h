@@ -220,8 +220,11 @@ struct Layout {
         K = p.K < p.n ? p.K : p.n;
         m = n - base;
         ldD = (n + 3) & ~3;
-        PR = panel_rows(n, flags);
-        KS = PR < n ? 1 : gram_splits(n, d);
+        // caller-supplied neighbour lists (GLL_FLAG_KNN_GIVEN, ingest.hip): no search, so no
+        // distance buffer, no pre-split planes, no locality order -- zero bytes each, PR = n
+        const bool given = (flags & GLL_FLAG_KNN_GIVEN) != 0;
+        PR = given ? n : panel_rows(n, flags);
+        KS = (given || PR < n) ? 1 : gram_splits(n, d);
         // reverse-list capacity: past it a row's reverse entries go to the global overflow
         // list, which each such (hub) row then scans whole -- at stress (K = 30) 4(K-1)+8 left
         // 39 hubs scanning 742 entries, 14 of their 35 us (profiles/r05w_trace_stress.txt)
@@ -240,7 +243,7 @@ struct Layout {
             return at;
         };
         status = take(size_t(kStWords) * 4);
-        D2 = take(size_t(KS) * PR * ldD * 4);  // KS partial planes (or one panel)
+        D2 = take(given ? 0 : size_t(KS) * PR * ldD * 4);  // KS partial planes (or one panel)
         knn_idx = take(size_t(n) * K * 4);
         knn_d2 = take(size_t(n) * K * 4);
         eps = take(size_t(n) * 4);
@@ -268,14 +271,14 @@ struct Layout {
         VRM = RV ? vr_max_per_row(K) : 0;
         vr = take(size_t(m) * VRM * kVrSlot);
         dp = (d + 63) & ~63;
-        xhi = take(size_t(n) * dp * 2);
-        xlo = take(size_t(n) * dp * 2);
-        xnrm = take(size_t(n) * 4);
+        xhi = take(given ? 0 : size_t(n) * dp * 2);
+        xlo = take(given ? 0 : size_t(n) * dp * 2);
+        xnrm = take(given ? 0 : size_t(n) * 4);
         fsync = take(512);   // four words on their own 128-B lines, zeroed by row_build
-        d2s = take(256);     // fp16 D2 scale of the pre-split Gram (gram.hip tile_d2_scale)
-        pid = take(size_t(n) * 4);
-        perm = take(size_t(n) * 4);
-        ohist = take(size_t((n + 63) / 64) * 64 * 4);
+        d2s = take(given ? 0 : 256);   // fp16 D2 scale of the pre-split Gram (gram.hip tile_d2_scale)
+        pid = take(given ? 0 : size_t(n) * 4);
+        perm = take(given ? 0 : size_t(n) * 4);
+        ohist = take(given ? 0 : size_t((n + 63) / 64) * 64 * 4);
         P = take(size_t(n) * C * 4);       // [Y; U] as fp32 (backward's P, GLL.py:109)
         Wadj = take(size_t(n) * C * 4);    // [0; Luu^-1 gbar] (backward's w, GLL.py:104)
         S = take(size_t(Etot) * 4);        // per-edge coefficient (auto eps / chunked gradient)
@@ -605,9 +608,16 @@ hipError_t launch_gram_panel(const Layout& L, void* ws, const float* X, bool vec
 // L2 (n d 4 B > 4 MB), with the whole n x n distance matrix (no row panels).
 inline bool locality_order(const Layout& L, const Batch& bt) {
     return bt.B == 1 && L.PR == L.n && L.n >= 16 * kPiv &&
-           size_t(L.n) * L.d * 4 > (size_t(4) << 20) && !(L.flags & GLL_FLAG_ROW_ORDER_OFF);
+           size_t(L.n) * L.d * 4 > (size_t(4) << 20) &&
+           !(L.flags & (GLL_FLAG_ROW_ORDER_OFF | GLL_FLAG_KNN_GIVEN));
 }
 hipError_t launch_order(const Layout& L, void* ws, hipStream_t s);
+// Caller-supplied neighbour lists in place of gram + select (ingest.hip): a reset
+// of the per-call counters, then one wave per row writes knn_idx / knn_d2 / eps and the reverse
+// entries the select would have written.  nbr: graph 0's n x (K - 1) int32 lists, graph after graph.
+hipError_t launch_ingest(const Layout& L, const Batch& bt, void* ws, const float* X,
+                         const int32_t* nbr, float eps_fixed, bool auto_eps, bool vec,
+                         int32_t* status_pub, hipStream_t s);
 // The Luu solves of this problem try the whole-GPU CG first (solve.hip cg_dispatch): single
 // graphs past the per-column kernels' sweet spot (m > 2048), or forced by GLL_FLAG_CG_GRID.
 inline bool grid_cg_route(const Layout& L, const Batch& bt) {

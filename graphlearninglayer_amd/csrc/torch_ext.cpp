@@ -24,6 +24,9 @@
 //     call followed by the score/objective head (gll_objective_head_batched: the weighted
 //     cross-entropy / entropy / l2 loss and the score store of FullySup.py:165-175 in one kernel),
 //     on the same node;
+//   * neighbors= (the last argument of all four): the caller's neighbour lists instead of the
+//     search -- gll_forward_lists_batched with GLL_FLAG_KNN_GIVEN; the node, the
+//     heads and the parameter gradients are the same;
 //   * the front end: an fp32 X with normalize=False goes to the kernels as it is;
 //     normalize=True, or an fp16 / bf16 X, takes one gll_features_forward launch into a fresh fp32
 //     X^ (and rnorm), which the node saves instead of X, and one gll_features_backward launch that
@@ -123,6 +126,10 @@ void report(const int32_t* st) {
                     " whole-GPU CG solve(s) lost their grid barrier (other kernels held the "
                     "CUs) and were solved by one workgroup instead: correct, slower");
     if (st[GLL_ST_TINY_EPS]) warn_py(PyExc_UserWarning, "Epsilon in KNN is very close to zero.");
+    if (st[GLL_ST_LIST_DROPPED])
+        warn_py(PyExc_UserWarning,
+                "GLL neighbors: " + std::to_string(st[GLL_ST_LIST_DROPPED]) +
+                    " list entries were dropped (an index outside [0, n) or a repeat within a row)");
     if (st[GLL_ST_FWD_NONCONV])
         warn_py(PyExc_RuntimeWarning,
                 "GLL forward CG: " + std::to_string(st[GLL_ST_FWD_NONCONV]) +
@@ -402,7 +409,7 @@ struct LaplaceBackward : public torch::autograd::Node {
 };
 
 // ------------------------------------------------------------------------------------------
-// apply(X, label_matrix, tau=0, epsilon='auto', k=25, normalize=False)        GLL.py:14-73
+// apply(X, label_matrix, tau=0, epsilon='auto', k=25, normalize=False, neighbors=None)  GLL.py:14-73
 // ------------------------------------------------------------------------------------------
 double parse_float(PyObject* o, const char* what) {
     const double v = PyFloat_AsDouble(o);
@@ -496,7 +503,7 @@ struct LayerCall {
 };
 
 void layer_forward(LayerCall& c, const char* fn, PyObject* aX, PyObject* aY, PyObject* atau,
-                   PyObject* aeps, PyObject* ak, PyObject* anorm) {
+                   PyObject* aeps, PyObject* ak, PyObject* anorm, PyObject* anbr) {
     if (!aX || !aY) raise_py(PyExc_TypeError, std::string(fn) + "() needs X and label_matrix");
     c.X = tensor_arg(aX, "X");
     c.Y = tensor_arg(aY, "label_matrix");
@@ -527,6 +534,21 @@ void layer_forward(LayerCall& c, const char* fn, PyObject* aX, PyObject* aY, PyO
         raise_py(PyExc_ValueError, "k = " + std::to_string(k) + " (n = " + std::to_string(n) +
                                        "): the kNN count incl. self must satisfy 2 <= min(k, n) <= " +
                                        std::to_string(kMaxK));
+    // neighbors: the caller's lists in place of the search: n x K (the
+    // reference's knn_ind, column 0 = self, not read) or n x (K - 1), with X's leading B; checked
+    // on metadata alone, before any GPU call
+    at::Tensor nbr;
+    if (anbr && anbr != Py_None) {
+        nbr = tensor_arg(anbr, "neighbors");
+        const int64_t w = nbr.dim() >= 1 ? nbr.size(-1) : -1;
+        if (!at::isIntegralType(nbr.scalar_type(), false))
+            raise_py(PyExc_ValueError, "neighbors must hold integers (int32 or int64)");
+        if (nbr.dim() != X.dim() || nbr.size(-2) != n || (X.dim() == 3 && nbr.size(0) != X.size(0)) ||
+            (w != kk && w != kk - 1))
+            raise_py(PyExc_ValueError,
+                     "neighbors must be " + std::string(X.dim() == 3 ? "B x " : "") + "n x k or n x (k - 1) = " +
+                         std::to_string(n) + " x " + std::to_string(kk) + " or " + std::to_string(kk - 1));
+    }
     // device: X's, or the current one for CPU input (the result goes back to the CPU)
     int devi;
     if (X.is_cuda()) {
@@ -572,6 +594,12 @@ void layer_forward(LayerCall& c, const char* fn, PyObject* aX, PyObject* aY, PyO
                                        " != " + std::to_string(B));
     if (!Yd.is_contiguous()) Yd = Yd.contiguous();
     c.p = make_problem(n, d, base, C, k, tau, eps, st.sink.data_ptr<int32_t>());
+    if (nbr.defined()) {
+        c.p.flags |= GLL_FLAG_KNN_GIVEN;   // no distance buffer in the workspace
+        nbr = nbr.detach();
+        if (nbr.size(-1) == kk) nbr = nbr.narrow(-1, 1, kk - 1);   // drop the self column
+        nbr = nbr.to(dev, at::kInt).contiguous();
+    }
     const size_t nb = gll_workspace_bytes(&c.p);
     if (nb == 0)
         raise_py(PyExc_ValueError, "unsupported GLL problem n=" + std::to_string(n) + " d=" +
@@ -581,9 +609,15 @@ void layer_forward(LayerCall& c, const char* fn, PyObject* aX, PyObject* aY, PyO
     c.ws = at::empty({int64_t(nb) * B}, opts.dtype(at::kByte));
     c.U = batched ? at::empty({B, n - base, C}, opts.dtype(at::kDouble))
                   : at::empty({n - base, C}, opts.dtype(at::kDouble));
-    check_rc(gll_forward_batched(&c.p, int(B), c.X32.data_ptr<float>(), Yd.data_ptr(), ycode,
-                                 c.ws.data_ptr(), c.U.data_ptr<double>(), c.s),
-             "gll_forward");
+    if (nbr.defined())
+        check_rc(gll_forward_lists_batched(&c.p, int(B), c.X32.data_ptr<float>(),
+                                           nbr.data_ptr<int32_t>(), Yd.data_ptr(), ycode,
+                                           c.ws.data_ptr(), c.U.data_ptr<double>(), c.s),
+                 "gll_forward_lists");
+    else
+        check_rc(gll_forward_batched(&c.p, int(B), c.X32.data_ptr<float>(), Yd.data_ptr(), ycode,
+                                     c.ws.data_ptr(), c.U.data_ptr<double>(), c.s),
+                 "gll_forward");
     after_call(st, devi, c.s);
     c.B = B;
     c.n = n;
@@ -624,11 +658,12 @@ std::shared_ptr<LaplaceBackward> make_node(LayerCall& c, const std::vector<at::T
 }
 
 PyObject* apply_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames) {
-    static const char* names[] = {"X", "label_matrix", "tau", "epsilon", "k", "normalize"};
-    PyObject* a[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    collect_args("apply", names, 6, args, nargs, kwnames, a);
+    static const char* names[] = {"X", "label_matrix", "tau", "epsilon", "k", "normalize",
+                                  "neighbors"};
+    PyObject* a[7] = {};
+    collect_args("apply", names, 7, args, nargs, kwnames, a);
     LayerCall c;
-    layer_forward(c, "apply", a[0], a[1], a[2], a[3], a[4], a[5]);
+    layer_forward(c, "apply", a[0], a[1], a[2], a[3], a[4], a[5], a[6]);
     const std::vector<at::Tensor> inputs = grad_inputs(c);
     if (torch::autograd::compute_requires_grad(inputs))
         torch::autograd::set_history(c.U, make_node(c, inputs));
@@ -673,15 +708,16 @@ PyObject* head_result(LayerCall& c, const std::vector<at::Tensor>& inputs, at::T
 // dloss/dU, which the node keeps: its backward is the layer's, fed gbar * grad_loss.
 // ------------------------------------------------------------------------------------------
 PyObject* ce_loss_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames) {
-    static const char* names[] = {"X", "label_matrix", "targets", "tau", "epsilon", "k", "normalize"};
-    PyObject* a[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    collect_args("ce_loss", names, 7, args, nargs, kwnames, a);
+    static const char* names[] = {"X", "label_matrix", "targets", "tau", "epsilon", "k", "normalize",
+                                  "neighbors"};
+    PyObject* a[8] = {};
+    collect_args("ce_loss", names, 8, args, nargs, kwnames, a);
     if (!a[2]) raise_py(PyExc_TypeError, "ce_loss() needs targets");
     const at::Tensor& T = tensor_arg(a[2], "targets");
     if (!at::isIntegralType(T.scalar_type(), false))
         raise_py(PyExc_TypeError, "targets must hold integers");
     LayerCall c;
-    layer_forward(c, "ce_loss", a[0], a[1], a[3], a[4], a[5], a[6]);
+    layer_forward(c, "ce_loss", a[0], a[1], a[3], a[4], a[5], a[6], a[7]);
     const int64_t m = c.n - c.base;
     at::Tensor Td = head_rows_arg(c, T, "targets");
     const auto f64 = c.X32.options().dtype(at::kDouble);
@@ -714,9 +750,10 @@ PyObject* ce_loss_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwname
 // wanted -- dloss/dU for the same node ce_loss uses.  other = None: the top-2 query alone.
 // ------------------------------------------------------------------------------------------
 PyObject* margin_loss_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames) {
-    static const char* names[] = {"X", "label_matrix", "other", "tau", "epsilon", "k", "normalize"};
-    PyObject* a[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    collect_args("margin_loss", names, 7, args, nargs, kwnames, a);
+    static const char* names[] = {"X", "label_matrix", "other", "tau", "epsilon", "k", "normalize",
+                                  "neighbors"};
+    PyObject* a[8] = {};
+    collect_args("margin_loss", names, 8, args, nargs, kwnames, a);
     if (!a[2]) raise_py(PyExc_TypeError, "margin_loss() needs other (a tensor of integers or None)");
     at::Tensor T;   // undefined: other = None
     if (a[2] != Py_None) {
@@ -725,7 +762,7 @@ PyObject* margin_loss_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kw
             raise_py(PyExc_TypeError, "other must hold integers (or be None)");
     }
     LayerCall c;
-    layer_forward(c, "margin_loss", a[0], a[1], a[3], a[4], a[5], a[6]);
+    layer_forward(c, "margin_loss", a[0], a[1], a[3], a[4], a[5], a[6], a[7]);
     const int64_t m = c.n - c.base;
     at::Tensor Td;
     if (T.defined()) Td = head_rows_arg(c, T, "other");
@@ -764,9 +801,10 @@ PyObject* margin_loss_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kw
 // ------------------------------------------------------------------------------------------
 PyObject* objective_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwnames) {
     static const char* names[] = {"X", "label_matrix", "targets", "tau", "epsilon", "k",
-                                  "normalize", "weights", "score", "score_out", "indices"};
-    PyObject* a[11] = {};
-    collect_args("objective", names, 11, args, nargs, kwnames, a);
+                                  "normalize", "weights", "score", "score_out", "indices",
+                                  "neighbors"};
+    PyObject* a[12] = {};
+    collect_args("objective", names, 12, args, nargs, kwnames, a);
     if (!a[2]) raise_py(PyExc_TypeError, "objective() needs targets (a tensor of integers or None)");
     at::Tensor T;   // undefined: targets = None
     if (a[2] != Py_None) {
@@ -814,7 +852,7 @@ PyObject* objective_impl(PyObject* const* args, Py_ssize_t nargs, PyObject* kwna
         kind = GLL_SCORE_NONE;   // a score without a store: nothing to scatter
     }
     LayerCall c;
-    layer_forward(c, "objective", a[0], a[1], a[3], a[4], a[5], a[6]);
+    layer_forward(c, "objective", a[0], a[1], a[3], a[4], a[5], a[6], a[11]);
     if (has_out && S.device().index() != c.devi)
         raise_py(PyExc_ValueError,
                  "score_out must be a contiguous float32 tensor of shape N on the layer's device");
@@ -867,11 +905,14 @@ PyMethodDef kApplyDef = {
     "apply", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(entry_py<apply_impl>)),
     METH_FASTCALL | METH_KEYWORDS,
     "U = LaplaceLearningSparseHard.apply(X, label_matrix, tau=0, epsilon='auto', k=25,\n"
-    "                                    normalize=False)\n"
+    "                                    normalize=False, neighbors=None)\n"
     "(GLL.py:14; k: neighbours incl. self, the reference hard-codes 25; normalize=True: the rows\n"
     "of X are scaled to unit length first, as F.normalize(X, dim=1) does).  X, a floating-point\n"
     "label_matrix and tau / a fixed epsilon given as one-element tensors are differentiable\n"
-    "(a tensor's value is read once in the forward: a host sync when it lives on the GPU)"};
+    "(a tensor's value is read once in the forward: a host sync when it lives on the GPU).\n"
+    "neighbors: an integer tensor n x k (the reference's knn_ind, column 0 = self) or n x (k - 1)\n"
+    "(B x ... for batched X): the graph is built from these lists in the caller's order instead of\n"
+    "a search, with no n x n distance buffer; ce_loss, margin_loss and objective take it too"};
 
 PyMethodDef kCeLossDef = {
     "ce_loss", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(entry_py<ce_loss_impl>)),

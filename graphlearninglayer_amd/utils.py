@@ -37,7 +37,8 @@ def one_hot_encode(labels, n_classes="auto"):
     return one_hot
 
 
-def _laplace_device(X, train_labels, knn_num, epsilon, n_classes, tau, tol, max_iter):
+def _laplace_device(X, train_labels, knn_num, epsilon, n_classes, tau, tol, max_iter,
+                    neighbors=None):
     """The graph build and solve of laplace: (X as given, as a tensor; the one-hot labels; the
     m x C float64 solution on the device; the graph's eps)."""
     Xt = X if torch.is_tensor(X) else torch.from_numpy(np.ascontiguousarray(X))
@@ -47,7 +48,8 @@ def _laplace_device(X, train_labels, knn_num, epsilon, n_classes, tau, tol, max_
     n = Xt.shape[0]
     m = n - k
     with torch.cuda.device(dev):
-        g = GLL.device_graph(Xt, knn_num, epsilon)            # W of knn_sym_dist, utils.py:574
+        # W of knn_sym_dist, utils.py:574 (neighbors: the caller's lists, no n x n buffer)
+        g = GLL.device_graph(Xt, knn_num, epsilon, neighbors=neighbors)
         rp, col = g["row_ptr"].long(), g["col"].long()
         w = g["w"].double()
         eps = g["eps"].clone()
@@ -80,24 +82,26 @@ def _laplace_device(X, train_labels, knn_num, epsilon, n_classes, tau, tol, max_
 
 
 def laplace(X, train_labels, knn_num=50, epsilon="auto", n_classes="auto", tau=1e-8,
-            tol=1e-10, max_iter=100000):
+            tol=1e-10, max_iter=100000, neighbors=None):
     """utils.py:570-593 on the GPU: labeled rows of X first (the reference: 'labeled indices
-    are 0,1,2,...,k-1').  Returns the m x C float64 prediction of the unlabeled rows."""
+    are 0,1,2,...,k-1').  Returns the m x C float64 prediction of the unlabeled rows.
+    neighbors: the caller's lists (GLL.device_graph) instead of the exact search, e.g. from an
+    approximate index as the reference's own."""
     return _laplace_device(X, train_labels, knn_num, epsilon, n_classes, tau, tol,
-                           max_iter)[2].cpu().numpy()
+                           max_iter, neighbors)[2].cpu().numpy()
 
 
 LaplaceFit = collections.namedtuple("LaplaceFit", "X P eps epsilon")
 
 
 def laplace_fit(X, train_labels, knn_num=50, epsilon="auto", n_classes="auto", tau=1e-8,
-                tol=1e-10, max_iter=100000):
+                tol=1e-10, max_iter=100000, neighbors=None):
     """Laplace learning on X (labeled rows first) as `laplace` runs it, kept on the device for
     laplace_predict: LaplaceFit(X, P, eps, epsilon) with X the n x d float32 features, P = [Y; U]
     the n x C float32 predictions (one-hot labels, then the solution) and eps the graph's n
     eps_i (the fixed epsilon n times, or the 'auto' kth-neighbour distances)."""
     Xt, Y, x, eps = _laplace_device(X, train_labels, knn_num, epsilon, n_classes, tau, tol,
-                                    max_iter)
+                                    max_iter, neighbors)
     dev = x.device
     with torch.cuda.device(dev):
         P = torch.cat([torch.from_numpy(Y).to(dev), x]).float()
@@ -129,13 +133,13 @@ def gl_accuracy_inductive(train_data, train_label, test_data, test_label, unlabe
 
 
 def gl_accuracy(train_data, train_label, test_data, test_label, unlabeled_data=None,
-                epsilon=1.0, tau=1e-8, knn_num=50):
+                epsilon=1.0, tau=1e-8, knn_num=50, neighbors=None):
     """The numerical part of test_GL_NP (utils.py:637-660) on feature arrays: Laplace learning
     on [train; unlabeled; test], accuracy (%) of argmax on the test rows."""
     parts = [train_data] + ([unlabeled_data] if unlabeled_data is not None else []) + [test_data]
     all_data = np.concatenate([np.asarray(p, dtype=np.float32) for p in parts], axis=0)
     U = laplace(all_data, np.asarray(train_label), knn_num=knn_num, epsilon=epsilon,
-                n_classes="auto", tau=tau)
+                n_classes="auto", tau=tau, neighbors=neighbors)
     pred = np.argmax(U, axis=1)
     correct = int(np.sum(pred[-len(test_data):] == np.asarray(test_label)))
     return 100.0 * correct / len(test_data)

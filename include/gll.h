@@ -60,6 +60,10 @@ extern "C" {
 #define GLL_ST_GRAD_SPLIT 12   /* rows the last fused backward (cg_grad_fused_kernel) ran as 2 or 4
                                 * waves, each over a part of the row's features (diagnostic: the
                                 * gradient is bitwise the same either way; 0 when rows ran whole) */
+#define GLL_ST_LIST_DROPPED 13 /* entries of caller-supplied neighbour lists (gll_forward_lists_batched,
+                                * gll_graph_lists) that were dropped and the caller should hear
+                                * about: an index outside [0, n), or a repeat of an earlier entry of
+                                * the same row (count; the Python layer warns) */
 #define GLL_ST_NWORDS 16
 
 /* gll_problem.flags: code-path choices for tests and A/B runs; none changes a result beyond
@@ -91,8 +95,15 @@ extern "C" {
 #define GLL_FLAG_ROW_ORDER_OFF 262144 /* large single graphs: process the kNN select and the
                                        * chunked gradient in row-index order instead of the
                                        * pivot-grouped locality order (A/B; results identical) */
+#define GLL_FLAG_KNN_GIVEN 524288  /* the neighbour lists come from the caller (gll_forward_lists_batched,
+                                    * gll_graph_lists): no search, and the workspace holds no distance
+                                    * buffer, Gram planes or locality order -- gll_workspace_bytes loses
+                                    * its n x n term.  Unlike the flags above it belongs to the problem:
+                                    * every call on that workspace carries it.  GLL_ERR_INVALID_ARG
+                                    * together with a flag that only steers the search (KNN_PANEL,
+                                    * GRAM_INLINE, D2_F32, ROW_ORDER_OFF) */
 #define GLL_FLAG_ALL (1 | 8 | 128 | 256 | 512 | 1024 | 2048 | 4096 | 8192 | 16384 | 65536 | \
-                      131072 | 262144)
+                      131072 | 262144 | 524288)
 /* (Retired, rejected with GLL_ERR_INVALID_ARG: 2 GRAM_NARROW, 4 CG_CLASSIC, 16 GRAM_F32,
  * 32 CG_PIPE, 64 GRAM_NOSPLIT, 32768 CG_PAIRS -- variants that lost their A/B runs.) */
 
@@ -635,6 +646,37 @@ int gll_extend_backward(int64_t Q, int64_t N, int32_t kn, int32_t d, int32_t C,
                         float* gXq, float* gXdb, float* gP, double* grad_eps,
                         int32_t* status, void* workspace, void* stream);
 int64_t gll_extend_grad_launches(void);  /* kernel launches of gll_extend_backward so far in this process (host counter) */
+
+/* The layer on caller-supplied neighbour lists (ingest.hip).  The reference defines
+ * every stage after the neighbour search on an arbitrary knn_ind (GLL.py:186-205: the symmetrisation
+ * by the larger directed distance, eps_i = the distance to the entry in the last column, then the
+ * weights, the Laplacian and both solves); these entry points start there.  p->flags must hold
+ * GLL_FLAG_KNN_GIVEN (and gll_forward* / gll_graph refuse it), so the workspace has no n x n term.
+ * nbr: B x n x (K - 1) int32 device memory, K = min(p->K, n): for every row the OTHER rows, in the
+ * caller's order, which is kept -- column K - 2 is the reference's knn_ind[:, -1], the 'auto'
+ * eps_i and the kth-neighbour term of the gradient come from it.  Per row, one wave:
+ *   d2_ij = sum_f (x_if - x_jf)^2 in float64 over the fp32 features, rounded once to fp32 (the wide
+ *           select's and gll_knn_query's contract; bitwise symmetric in (i, j))
+ *   dropped and counted in GLL_ST_LIST_DROPPED: an index outside [0, n); a repeat of an earlier
+ *           entry of the row (the reference would sum a duplicate's distance in coo -> csr)
+ *   dropped silently: the row itself, d2 = 0 (a duplicated point), a non-finite d2 -- as the
+ *           search drops them and sparse.find does (GLL.py:198)
+ *   kept entries stay in the caller's order at the front of knn_idx / knn_d2 row i (column 0 is
+ *   (i, 0), the self slot), the tail is padded with (i, 0) as the search pads a row with fewer
+ *   valid candidates; eps_i = p->eps, or for 'auto' sqrtf(knn_d2[i][K - 1]) -- a padded last
+ *   column gives 0 and GLL_ST_TINY_EPS (GLL.py:240-241).
+ * Then the row build and, for the forward, the Luu solve, exactly as after a search: launches =
+ * one reset, the ingest, the row build (+ the CG).  Everything downstream (gll_backward_batched,
+ * gll_param_grad_batched, the three heads, gll_workspace_view) takes the same problem and workspace.
+ * No floating-point atomics; knn_idx, knn_d2 and eps are bitwise reproducible, and so is everything
+ * after them (the row build sorts each row by column).  Any list is accepted -- e.g. one column
+ * named by every row: a row's reverse entries past RCAP go through the overflow list, rows longer
+ * than a slot through the bump region, whose sizes (n (K - 1) triples, 2 n (K - 1) entries) bound any
+ * list.  nbr == NULL is GLL_ERR_INVALID_ARG before any GPU call.  gll_graph_lists needs base == 0. */
+int gll_forward_lists_batched(const gll_problem* p, int B, const float* X, const int32_t* nbr,
+                              const void* Y, int y_dtype, void* workspace, double* U, void* stream);
+int gll_graph_lists(const gll_problem* p, const float* X, const int32_t* nbr, void* workspace,
+                    void* stream);
 
 #ifdef __cplusplus
 }
