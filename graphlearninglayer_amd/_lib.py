@@ -92,7 +92,7 @@ EXPORTS = (
     "gll_supcon_scratch_bytes", "gll_supcon_forward", "gll_supcon_backward", "gll_supcon_launches",
     "gll_query_workspace_bytes", "gll_knn_query", "gll_extend", "gll_query_launches",
     "gll_extend_grad_workspace_bytes", "gll_extend_backward", "gll_extend_grad_launches",
-    "gll_forward_lists_batched", "gll_graph_lists",
+    "gll_forward_lists_batched", "gll_graph_lists", "gll_cg_route",
 )
 
 
@@ -184,6 +184,8 @@ def _declare(lib):
     lib.gll_kernel_name.restype = ct.c_char_p
     lib.gll_select_route.argtypes = [ct.POINTER(Problem), i32, i32, i32, ct.POINTER(ct.c_int32)]
     lib.gll_select_route.restype = i32
+    lib.gll_cg_route.argtypes = [ct.POINTER(Problem), i32, ct.POINTER(ct.c_int32)]
+    lib.gll_cg_route.restype = i32
     lib.gll_fused_plan.argtypes = [ct.POINTER(Problem), i32, i32, ct.POINTER(ct.c_int32)]
     lib.gll_fused_plan.restype = i32
     lib.gll_set_knob.argtypes = [i32, i32]

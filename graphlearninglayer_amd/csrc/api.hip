@@ -1,6 +1,6 @@
 // api.hip -- the extern "C" boundary declared in include/gll.h.
 //
-// Orchestrates the kernels of gram.hip, select.hip, order.hip, ingest.hip, rows.hip, solve.hip / gridcg.hip,
+// Orchestrates the kernels of gram.hip, select.hip, order.hip, ingest.hip, rows.hip, solve.hip / fused_bwd.hip / gridcg.hip,
 // grad.hip, param_grad.hip, loss.hip and features.hip on the caller's stream.  No allocation, no host synchronisation: the caller owns the workspace (the
 // Python mirror takes it from torch's caching allocator) and keeps it alive from
 // gll_forward to gll_backward, as the reference keeps its graph on ctx (GLL.py:69-70).
@@ -12,6 +12,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "cg_route.h"
 #include "knn_route.h"
 
 namespace gll {
@@ -702,6 +703,21 @@ int gll_fused_plan(const gll_problem* p, int x_aligned, int capacity,
                                                                              : GLL_ERR_UNSUPPORTED;
 }
 
+int gll_cg_route(const gll_problem* p, int B, int32_t out[GLL_CG_ROUTE_WORDS]) {
+    int rc = check(p);
+    if (rc != GLL_OK) return rc;
+    if (B < 1 || B > 65535 || !out) return GLL_ERR_INVALID_ARG;
+    Layout L(*p);
+    Batch bt;
+    bt.B = B;
+    const CgRoute rt = cg_route(L, bt);
+    const int32_t words[GLL_CG_ROUTE_WORDS] = {rt.grid_first, rt.family,     rt.NT,
+                                               rt.R,          rt.S,          rt.MODE,
+                                               rt.vec_in_lds, cg_table_index(rt), cg_table_rows()};
+    for (int q = 0; q < GLL_CG_ROUTE_WORDS; ++q) out[q] = words[q];
+    return words[7] >= 0 ? GLL_OK : GLL_ERR_UNSUPPORTED;
+}
+
 #ifndef GLL_BUILD_ID
 #define GLL_BUILD_ID "unknown"
 #endif
@@ -721,7 +737,8 @@ const char* gll_strerror(int code) {
 
 #ifdef GLL_TRACE
 // Diagnostic build only (libgll_trace.so): in-kernel timestamps per translation unit
-// (0 knn = gram.hip, 1 rows, 2 solve, 3 grad, 4 gridcg, 5 select), see GLL_TRACE_UNIT in
+// (0 knn = gram.hip, 1 rows, 2 solve, 3 grad, 4 gridcg, 5 select, 6 fused = fused_bwd.hip), see
+// GLL_TRACE_UNIT in
 // gll_internal.h.
 namespace gll {
 void trace_read_knn(unsigned long long*);
@@ -730,16 +747,19 @@ void trace_read_solve(unsigned long long*);
 void trace_read_grad(unsigned long long*);
 void trace_read_gridcg(unsigned long long*);
 void trace_read_select(unsigned long long*);
+void trace_read_fused(unsigned long long*);
 void trace_reset_gridcg();
 void trace_read_wg_knn(unsigned long long*);
 void trace_read_wg_solve(unsigned long long*);
 void trace_read_wg_gridcg(unsigned long long*);
 void trace_read_wg_select(unsigned long long*);
+void trace_read_wg_fused(unsigned long long*);
 void trace_reset_knn();
 void trace_reset_rows();
 void trace_reset_solve();
 void trace_reset_grad();
 void trace_reset_select();
+void trace_reset_fused();
 }  // namespace gll
 
 extern "C" int gll_trace_read(int unit, unsigned long long* out) {
@@ -751,6 +771,7 @@ extern "C" int gll_trace_read(int unit, unsigned long long* out) {
         case 3: gll::trace_read_grad(out); return GLL_OK;
         case 4: gll::trace_read_gridcg(out); return GLL_OK;
         case 5: gll::trace_read_select(out); return GLL_OK;
+        case 6: gll::trace_read_fused(out); return GLL_OK;
         default: return GLL_ERR_INVALID_ARG;
     }
 }
@@ -762,6 +783,7 @@ extern "C" int gll_trace_read_wg(int unit, unsigned long long* out) {
         case 2: gll::trace_read_wg_solve(out); return GLL_OK;
         case 4: gll::trace_read_wg_gridcg(out); return GLL_OK;
         case 5: gll::trace_read_wg_select(out); return GLL_OK;
+        case 6: gll::trace_read_wg_fused(out); return GLL_OK;
         default: return GLL_ERR_INVALID_ARG;
     }
 }
@@ -782,6 +804,7 @@ extern "C" int gll_trace_reset(int unit) {
         case 3: gll::trace_reset_grad(); return GLL_OK;
         case 4: gll::trace_reset_gridcg(); return GLL_OK;
         case 5: gll::trace_reset_select(); return GLL_OK;
+        case 6: gll::trace_reset_fused(); return GLL_OK;
         default: return GLL_ERR_INVALID_ARG;
     }
 }

@@ -183,7 +183,7 @@ inline int panel_rows(int n, int flags) {
 
 size_t grid_cg_workspace_floats(int m, int C);
 // The whole-GPU CG's sync words at the start of its region (gridcg.hip kSyncWords): row_build
-// zeroes them before a forward whose solves take that kernel (grid_cg_route), and each solve
+// zeroes them before a forward whose solves take that kernel (cg_route.h grid_cg_route), and each solve
 // leaves them zero, so its launch needs no memset.
 constexpr int kGridSyncWords = 2048;   // >= gridcg.hip kSyncWords
 struct Layout;
@@ -549,7 +549,7 @@ __device__ __forceinline__ T* gshift_br_at(T* p, size_t stride, int g) {
 hipError_t launch_status(const char* what);
 
 // Opt a kernel into all of the 160 KiB of LDS its static allocation leaves for dynamic use
-// (once per kernel; solve.hip).
+// (once per kernel; defined in solve.hip).
 void allow_full_lds(const void* fn);
 
 // Every kernel goes out through launch_k.  When prof_begin has armed an event pair for the next
@@ -618,12 +618,6 @@ hipError_t launch_order(const Layout& L, void* ws, hipStream_t s);
 hipError_t launch_ingest(const Layout& L, const Batch& bt, void* ws, const float* X,
                          const int32_t* nbr, float eps_fixed, bool auto_eps, bool vec,
                          int32_t* status_pub, hipStream_t s);
-// The Luu solves of this problem try the whole-GPU CG first (solve.hip cg_dispatch): single
-// graphs past the per-column kernels' sweet spot (m > 2048), or forced by GLL_FLAG_CG_GRID.
-inline bool grid_cg_route(const Layout& L, const Batch& bt) {
-    return bt.B == 1 && L.C <= 16 && !(L.flags & GLL_FLAG_CG_PERCOL) &&
-           (L.m > 2048 || (L.flags & GLL_FLAG_CG_GRID));
-}
 hipError_t launch_finalize(const Layout& L, const Batch& bt, void* ws, const void* Y,
                            int y_dtype, float tau, float eps_fixed, hipStream_t s);
 // b: right-hand sides of graph 0, `b_stride` bytes apart (the workspace rhs or gbar)
@@ -651,7 +645,7 @@ hipError_t launch_backward_grad(const Layout& L, const Batch& bt, void* ws, cons
                                 bool auto_eps, float eps_fixed, float* gradX, bool vec,
                                 hipStream_t s);
 // One small graph, fixed eps: the adjoint CG and the feature gradient in one launch
-// (solve.hip cg_grad_fused_kernel); hipErrorNotSupported when the shape does not qualify.
+// (fused_bwd.hip cg_grad_fused_kernel); hipErrorNotSupported when the shape does not qualify.
 hipError_t launch_cg_grad_fused(const Layout& L, void* ws, const void* gbar, int g_dtype,
                                 const float* X, float eps_fixed, float* gradX, float rtol,
                                 int max_iter, int32_t* st_nonconv, int32_t* st_iters,

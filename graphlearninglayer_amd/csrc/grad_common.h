@@ -1,5 +1,5 @@
 // grad_common.h -- per-edge pieces of the feature gradient shared by grad.hip and the fused
-// adjoint-CG + gradient kernel of solve.hip (closed form of GLL.py:111-159):
+// adjoint-CG + gradient kernel of fused_bwd.hip (closed form of GLL.py:111-159):
 //     G_ij = sum_c (w_ic - w_jc)(P_jc - P_ic),  V_ij = -8 W_ij / (eps_i eps_j)
 #pragma once
 

@@ -5,23 +5,19 @@
 // column runs its own PCG with per-column step sizes, and a column is frozen once it meets
 // its tolerance (GLL.py:258-268 masks alpha/beta the same way).
 //
-// cg_gv_kernel (round 3, the default), two forms on one machinery.  MODE 1, what every solve
-// runs: Chronopoulos-Gear single-reduction PCG, two grid barriers per iteration (u = M r
-// published, then the partial dot products (r,u), (w,u), (r,r)).  MODE 0, no longer dispatched:
-// pipelined PCG (Ghysels & Vanroose 2014, Alg. 4) -- ONE grid barrier per iteration: before it a
-// workgroup publishes m = M w with its partials; after it, the SpMV n = A m gathers the
-// published m while the partials are summed, and every vector update is local.  Its four extra
-// recurrences cost fp32 accuracy: the true residual of a Luu solve at m = 2100 ended at
-// 4-9e-6 ||b|| under rtol 1e-6 (tests/test_gpu_cg_contract.py), so the Luu solves left it for
-// MODE 1 (stress step 0.673 -> 0.720 ms, profiles/cg01_bench_ab.txt); the form stays in the
-// kernel for the barrier work DESIGN.md §9 names, which must pass that test to come back.
-// The workgroup's slice of the matrix (column byte offsets and values) is staged in LDS once
-// per solve, so an iteration reads nothing from global memory but the published vector and the
-// partials.  Rows past the LDS capacity read their entries from the CSR.
+// cg_gv_kernel (the default): Chronopoulos-Gear single-reduction PCG, two grid barriers per
+// iteration (u = M r published, then the partial dot products (r,u), (w,u), (r,r)).  The
+// workgroup's slice of the matrix (column byte offsets and values) is staged in LDS once per
+// solve, so an iteration reads nothing from global memory but the published vector and the
+// partials.  Rows past the LDS capacity read their entries from the CSR.  (The kernel's name
+// is from its first form, the pipelined PCG of Ghysels & Vanroose with one barrier per
+// iteration: its extra recurrences cost fp32 accuracy, the Luu solves left it in 5887a2a, and it
+// was deleted; DESIGN.md §3.2 and §9 say where it lives and what a
+// one-barrier form must pass to come back.)
 //
 // cg_grid_classic_kernel (rounds 1-2): classic two-reduction PCG, two grid barriers per
 // iteration, matrix entries and two vectors (z, p) gathered from global memory every iteration;
-// kept for systems past the pipelined kernel's 512 rows per workgroup (m > 131,072) and the
+// kept for systems past cg_gv_kernel's 512 rows per workgroup (m > 131,072) and the
 // oversubscription test.  Cross-workgroup hand-offs in both: DESIGN.md §3.5.
 //
 // Dot products: each workgroup writes its partial sums, and after the barrier EVERY
@@ -37,57 +33,25 @@
 namespace gll {
 
 GLL_TRACE_UNIT(gridcg)
+}  // namespace gll
+
+#include "cg_common.h"   // LuuRows, CsrRows
+
+namespace gll {
 
 constexpr int kGT = 256;   // threads per workgroup
 constexpr int kGCM = 16;   // columns held in registers (C <= kGCM)
 
-// Luu of the padded graph rows: row u is graph row base+u, its U block the sorted suffix of
-// length ucnt[u]; off-diagonal values -W, the diagonal deg + tau kept separately.
-struct LuuRows {
-    const int32_t* row_start;
-    const int32_t* row_len;
-    const int32_t* ucnt;
-    const int32_t* col;
-    const float* w;
-    const float* diag;
-    int base;
-    __device__ int begin(int u) const { return row_start[base + u] + row_len[base + u] - ucnt[u]; }
-    __device__ int end(int u) const { return row_start[base + u] + row_len[base + u]; }
-    __device__ int column(int e) const { return col[e] - base; }
-    __device__ float value(int e) const { return -w[e]; }
-    __device__ float diagonal(int u) const { return diag[u]; }
-    static constexpr bool kSeparateDiag = true;
-};
-
-// General CSR with the diagonal among the entries.
-struct CsrRows {
-    const int32_t* rp;
-    const int32_t* col;
-    const float* val;
-    __device__ int begin(int u) const { return rp[u]; }
-    __device__ int end(int u) const { return rp[u + 1]; }
-    __device__ int column(int e) const { return col[e]; }
-    __device__ float value(int e) const { return val[e]; }
-    __device__ float diagonal(int u) const {
-        float dg = 0.f;
-        for (int e = rp[u]; e < rp[u + 1]; ++e)
-            if (col[e] == u) dg += val[e];
-        return dg;
-    }
-    static constexpr bool kSeparateDiag = false;
-};
-
-struct GridCgArgs {
+// What a solve is, whichever grid kernel runs it: the launchers fill this, and each kernel's
+// argument struct begins with it (rescued() and rescue_solve read only this part).
+struct GridSolve {
     int m, C, Cp, max_iter;  // Cp: row stride of the published vectors (C rounded up to 4)
     float rtol, atol;        // per column: stop when ||r_c|| <= max(atol, rtol ||b_c||)
     const void* b;           // m x C right-hand sides, b_dtype
     int b_dtype;
     double* out64;           // m x C results (optional)
     float* out32;            // m x C results (optional)
-    float* Pbuf;             // 2 x m x Cp: p of the previous iteration (double-buffered)
-    float* Zbuf;             // m x Cp: z = M r of the previous iteration
-    float* part;             // [G][3][kGCM] partial sums
-    unsigned* sync;          // [0] arrivals, [1] failure word (zeroed before the launch)
+    unsigned* sync;          // the kernel's sync words (zero at launch)
     int rows_per_wg;
     int diag_fail;           // GLL_FLAG_DIAG_GRID_FAIL: inject a barrier failure (tests only)
     int32_t* st_iters;
@@ -95,7 +59,12 @@ struct GridCgArgs {
     int32_t* st_failed;      // public GLL_ST_SOLVE_FAILED word
     int32_t* st_rescued;     // public GLL_ST_GRID_RESCUED word
     float* rescue;           // 5 m floats: the rescue solve's vectors
-    int sync_zeroed;         // pipelined kernel: the sync words are known zero (no memset)
+};
+
+struct GridCgArgs : GridSolve {   // cg_grid_classic_kernel; sync: [0] arrivals, [1] failure word
+    float* Pbuf;             // 2 x m x Cp: p of the previous iteration (double-buffered)
+    float* Zbuf;             // m x Cp: z = M r of the previous iteration
+    float* part;             // [G][3][kGCM] partial sums
 };
 
 // Hand-off discipline: every byte another workgroup reads -- the published
@@ -611,9 +580,9 @@ __global__ __launch_bounds__(kGT) void cg_grid_classic_kernel(Mat A, GridCgArgs 
 }
 
 // ---------------------------------------------------------------------------------------
-// Pipelined whole-GPU PCG (cg_gv_kernel)
+// Chronopoulos-Gear whole-GPU PCG (cg_gv_kernel)
 // ---------------------------------------------------------------------------------------
-constexpr int kMaxG = 256;            // workgroups of one pipelined solve (<= one per CU)
+constexpr int kMaxG = 256;            // workgroups of one cg_gv solve (<= one per CU)
 constexpr int kGvMaxRows = 512;       // rows per workgroup: NG x RPG <= 64 x 8
 constexpr int kSyncLine = 32;         // words per sync word (one 128-B line each)
 // sync lines: [0, 8) group arrival counters, 8 top counter, 9 failure, 10 rescue, [11, 19)
@@ -629,33 +598,23 @@ constexpr int kSyncTop = kGvGroups, kSyncFail = kGvGroups + 1, kSyncRescue = kGv
 constexpr int kSyncWords = (2 * kGvGroups + 6) * kSyncLine;
 static_assert(kSyncWords <= kGridSyncWords, "gll_internal.h kGridSyncWords (row_build zeroes them)");
 
-struct GvArgs {
-    int m, C, Cp, NQ, PW, max_iter;   // PW: partial floats per workgroup (32 or 64)
-    float rtol, atol;                 // per column: stop when ||r_c|| <= max(atol, rtol ||b_c||)
-    const void* b;                    // m x C right-hand sides, b_dtype
-    int b_dtype;
-    double* out64;                    // m x C results (optional)
-    float* out32;                     // m x C results (optional)
-    float* V;                         // [2][m][Cp] published vectors (u0, then m_i), by parity
-    float* part;                      // [2][kMaxG][PW] partial sums, by parity
-    unsigned* sync;                   // kSyncWords: zero at launch (gv_exit leaves them so)
-    int rows_per_wg;
-    int lds_cap;                      // matrix entries the dynamic LDS slice holds
-    int hier;                         // two-level barrier (8 counters, then one)
-    int diag_fail;                    // GLL_FLAG_DIAG_GRID_FAIL (tests only)
-    int32_t* st_iters;
-    int32_t* st_nonconv;
-    int32_t* st_failed;
-    int32_t* st_rescued;
-    float* rescue;                    // 5 m floats: the rescue solve's vectors
+struct GvArgs : GridSolve {   // sync: kSyncWords, zero at launch (gv_exit leaves them so)
+    int NQ, PW;       // column quads, partial floats per workgroup (32 or 64)
+    float* V;         // [2][m][Cp] published vectors u, by parity
+    float* part;      // [2][kMaxG][PW] partial sums, by parity
+    int lds_cap;      // matrix entries the dynamic LDS slice holds
+    int hier;         // always 1: two-level arrivals (8 counters, then one); see gv_barrier
 };
 
-// Grid barrier of the pipelined kernel.  Every wave drains its sc1 stores (asm vmcnt(0): the
-// compiler does not count the buffer stores' completion by itself), the workgroup meets, and
-// thread 0 arrives (relaxed agent-scope atomics, performed at the memory side):
+// Grid barrier of cg_gv_kernel.  Every wave drains its sc1 stores (asm vmcnt(0): the compiler
+// does not count the buffer stores' completion by itself), the workgroup meets, and thread 0
+// arrives (relaxed agent-scope atomics, performed at the memory side):
 //  - hier: an add to arrival counter (block % 8) whose returned value tells the group's last
 //    arriver, which alone adds to the top counter (8 arrivals per epoch);
-//  - flat: an add to the top counter (G arrivals per epoch).
+//  - flat: an add to the top counter (G arrivals per epoch).  No launch takes this arm (it
+//    measured 116 against 74 us).  It stays because the kernel is better with it: without the
+//    branch every cg_gv_kernel instantiation takes 1-2 more VGPRs (or AGPRs, or 4 B more scratch
+//    where it spills), with the same argument layout either way (profiles/cs01_resources.txt).
 // The arrival that completes the top counter writes the epoch into the 8 release words, and
 // every workgroup polls its group's release word (sc1 loads, s_sleep): no poller reads a line
 // that atomics land on -- round 3 polled the top counter itself, 256 pollers on the line the
@@ -714,7 +673,7 @@ __device__ __forceinline__ bool gv_barrier(unsigned* sync, unsigned epoch, int G
     return *s_ok != 0;
 }
 
-// End of a pipelined solve: every workgroup counts out, and the last one returns the sync words
+// End of a cg_gv solve: every workgroup counts out, and the last one returns the sync words
 // to zero (every other workgroup of the grid has left, rescued or not), so the next solve on
 // this workspace starts from zero without a memset launch (row_build zeroes them before a
 // forward; gll_cg_csr's caller workspace still gets a memset).
@@ -755,14 +714,14 @@ constexpr int kOob = 0x7FFFFFF0;   // buffer offset past any num_records: the lo
 
 // Workgroup w owns rows [w R, (w+1) R).  A group of LPR lanes owns up to RPG of them (local
 // rows grp, grp + NG, ...); lane li of the group owns column quad li (columns 4li..4li+3) of
-// those rows and keeps x, r, u, w, p, s, q, z for them in registers for the whole solve.
+// those rows and keeps x, r, u, w, p, s for them in registers for the whole solve.
 // The group's lanes split each row's entries for the gathers and sum them by DPP.
-// MODE 0: pipelined PCG (Ghysels-Vanroose), one grid barrier per iteration.  MODE 1:
-// Chronopoulos-Gear single-reduction PCG on the same machinery, two barriers per iteration
-// (u published, then the partials): its recurrences keep fp32 attainable accuracy close to
-// classic PCG's, where GV's drift on ill-conditioned systems -- utils.laplace's tau = 1e-8 at
-// 60,250 points took 303 GV iterations against 92 (profiles/r03c_laplace_probe.txt).
-template <class Mat, int NT, int LPR, int RPG, int MODE>
+// Chronopoulos-Gear single-reduction PCG, two barriers per iteration (u published, then the
+// partials): its recurrences keep fp32 attainable accuracy close to classic PCG's, where the
+// one-barrier Ghysels-Vanroose form this kernel first ran drifted on ill-conditioned systems --
+// utils.laplace's tau = 1e-8 at 60,250 points took 303 of its iterations against 92
+// (profiles/r03c_laplace_probe.txt).
+template <class Mat, int NT, int LPR, int RPG>
 __global__ __launch_bounds__(NT) void cg_gv_kernel(Mat A, GvArgs a) {
     GLL_TRACE_SCOPE(1);
     extern __shared__ __attribute__((aligned(16))) int2 s_ent[];   // (byte offset, value bits)
@@ -883,12 +842,12 @@ __global__ __launch_bounds__(NT) void cg_gv_kernel(Mat A, GvArgs a) {
     };
 
     // ---- setup: x = 0, r = b (decoupled rows: 0), u = M r published for w = A u
-    f32x4 x[RPG], r[RPG], u[RPG], w[RPG], p[RPG], s[RPG], q[RPG], z[RPG];
+    f32x4 x[RPG], r[RPG], u[RPG], w[RPG], p[RPG], s[RPG];
     float mi[RPG], dg[RPG];
 #pragma unroll
     for (int k = 0; k < RPG; ++k) {
         const int uu = r0 + grp + k * NG;
-        x[k] = r[k] = u[k] = w[k] = p[k] = s[k] = q[k] = z[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+        x[k] = r[k] = u[k] = w[k] = p[k] = s[k] = f32x4{0.f, 0.f, 0.f, 0.f};
         mi[k] = dg[k] = 0.f;
         if (uu < r1) {
             dg[k] = A.diagonal(uu);
@@ -911,16 +870,6 @@ __global__ __launch_bounds__(NT) void cg_gv_kernel(Mat A, GvArgs a) {
     float gold_c = 1.f, aold_c = 1.f, tol2_c = 0.f;
     unsigned epoch = 0;
     bool ok = gv_barrier(a.sync, ++epoch, G, a.hier, &s_ok);
-    if constexpr (MODE == 0) {
-#pragma unroll
-        for (int k = 0; k < RPG; ++k) {
-            const int uu = r0 + grp + k * NG;
-            if (uu < r1) {
-                const f32x4 o = spmv(k, rv0);
-                w[k] = Mat::kSeparateDiag ? dg[k] * u[k] + o : o;
-            }
-        }
-    }
 
     int it = 0;
     GLL_TRACE_PT(8);
@@ -947,7 +896,7 @@ __global__ __launch_bounds__(NT) void cg_gv_kernel(Mat A, GvArgs a) {
         const int pub = (it + 1) & 1;
         const __amdgpu_buffer_rsrc_t rvp = pub ? rv1 : rv0;
         const __amdgpu_buffer_rsrc_t rpp = pub ? rpt1 : rpt0;
-        if constexpr (MODE == 1) {   // w = A u, u published before the last barrier
+        {   // w = A u, u published before the last barrier
             const __amdgpu_buffer_rsrc_t rvu = pub ? rv0 : rv1;
 #pragma unroll
             for (int k = 0; k < RPG; ++k) {
@@ -958,7 +907,7 @@ __global__ __launch_bounds__(NT) void cg_gv_kernel(Mat A, GvArgs a) {
                 }
             }
         }
-        // ---- local: partial (r,u), (w,u), (r,r); publish m = M w (pipelined form)
+        // ---- local: partial (r,u), (w,u), (r,r)
         {
             f32x4 pg = {0.f, 0.f, 0.f, 0.f}, pd = pg, pr = pg;
 #pragma unroll
@@ -968,9 +917,6 @@ __global__ __launch_bounds__(NT) void cg_gv_kernel(Mat A, GvArgs a) {
                     pg += r[k] * u[k];
                     pd += w[k] * u[k];
                     pr += r[k] * r[k];
-                    if constexpr (MODE == 0)
-                        __builtin_amdgcn_raw_buffer_store_b128(mi[k] * w[k], rvp,
-                                                               uu * rowB + 16 * li, 0, kSc1);
                 }
             }
             // lanes of one quad across the wave's row groups, then the waves in order
@@ -1009,23 +955,12 @@ __global__ __launch_bounds__(NT) void cg_gv_kernel(Mat A, GvArgs a) {
         if (a.diag_fail && it == 2) ok = false;   // injected failure (uniform over the grid)
         if (!ok) break;
         if (it == 0) GLL_TRACE_PT(9);
-        // ---- the partials of every workgroup (all loads in flight; out-of-range -> 0) ...
+        // ---- the partials of every workgroup (all loads in flight; out-of-range -> 0)
         const int NQP = PW / 4;
         f32x4 pl[JP];
 #pragma unroll
         for (int j = 0; j < JP; ++j)
             pl[j] = __builtin_amdgcn_raw_buffer_load_b128(rpp, (threadIdx.x + NT * j) * 16, 0, kSc1);
-        // ---- ... while n = A m gathers the published m
-        f32x4 nn[RPG];
-#pragma unroll
-        for (int k = 0; k < RPG; ++k) {
-            const int uu = r0 + grp + k * NG;
-            nn[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (MODE == 0 && uu < r1) {
-                const f32x4 o = spmv(k, rvp);
-                nn[k] = Mat::kSeparateDiag ? dg[k] * (mi[k] * w[k]) + o : o;
-            }
-        }
         GLL_GV_PT(14);
         // slot q = threadIdx % NQP: fixed order over j, then lanes, then waves
         {
@@ -1088,35 +1023,19 @@ __global__ __launch_bounds__(NT) void cg_gv_kernel(Mat A, GvArgs a) {
             al[t] = __shfl(al_c, (4 * li + t) & (kWave - 1));
             be[t] = __shfl(be_c, (4 * li + t) & (kWave - 1));
         }
-        if constexpr (MODE == 0) {   // ---- local updates (Ghysels-Vanroose recurrences)
+        // ---- Chronopoulos-Gear: p, s = A p by recurrence; u = M r published
 #pragma unroll
-            for (int k = 0; k < RPG; ++k) {
-                const int uu = r0 + grp + k * NG;
-                if (uu >= r1 || !qown) continue;
-                const f32x4 mk = mi[k] * w[k];
-                z[k] = nn[k] + be * z[k];
-                q[k] = mk + be * q[k];
-                s[k] = w[k] + be * s[k];
-                p[k] = u[k] + be * p[k];
-                x[k] += al * p[k];
-                r[k] -= al * s[k];
-                u[k] -= al * q[k];
-                w[k] -= al * z[k];
-            }
-        } else {   // ---- Chronopoulos-Gear: p, s = A p by recurrence; u = M r published
-#pragma unroll
-            for (int k = 0; k < RPG; ++k) {
-                const int uu = r0 + grp + k * NG;
-                if (uu >= r1 || !qown) continue;
-                p[k] = u[k] + be * p[k];
-                s[k] = w[k] + be * s[k];
-                x[k] += al * p[k];
-                r[k] -= al * s[k];
-                u[k] = mi[k] * r[k];
-                __builtin_amdgcn_raw_buffer_store_b128(u[k], rvp, uu * rowB + 16 * li, 0, kSc1);
-            }
-            ok = gv_barrier(a.sync, ++epoch, G, a.hier, &s_ok);
+        for (int k = 0; k < RPG; ++k) {
+            const int uu = r0 + grp + k * NG;
+            if (uu >= r1 || !qown) continue;
+            p[k] = u[k] + be * p[k];
+            s[k] = w[k] + be * s[k];
+            x[k] += al * p[k];
+            r[k] -= al * s[k];
+            u[k] = mi[k] * r[k];
+            __builtin_amdgcn_raw_buffer_store_b128(u[k], rvp, uu * rowB + 16 * li, 0, kSc1);
         }
+        ok = gv_barrier(a.sync, ++epoch, G, a.hier, &s_ok);
         GLL_GV_PT(17);
         ++it;
     }
@@ -1152,11 +1071,18 @@ __global__ __launch_bounds__(NT) void cg_gv_kernel(Mat A, GvArgs a) {
     gv_exit(a.sync, G, &s_ok);
 }
 
-size_t grid_cg_workspace_floats(int m, int C) {
+// Floats of the larger of the two kernels' regions (launch_grid and launch_gv carve them): the
+// sync words, the published vectors and the partial sums.
+static size_t grid_region_floats(int m, int C) {
     const size_t Cp = size_t((C + 3) & ~3);
     const size_t classic = 64 + size_t(3) * m * Cp + size_t(3) * kGCM * 1024;
     const size_t gv = kSyncWords + size_t(2) * m * Cp + size_t(2) * kMaxG * 64;
-    return (classic > gv ? classic : gv) + size_t(5) * m + 64;   // + the rescue vectors
+    return classic > gv ? classic : gv;
+}
+// The rescue vectors (5 m floats) sit past both regions, 256-B aligned.
+static size_t rescue_offset(int m, int C) { return (grid_region_floats(m, C) + 63) & ~size_t(63); }
+size_t grid_cg_workspace_floats(int m, int C) {
+    return grid_region_floats(m, C) + size_t(5) * m + 64;
 }
 
 // Workgroups of one kernel instance that can be resident at once on the whole device (the
@@ -1170,14 +1096,6 @@ static int coresident_capacity() {
         cap = (nb > 0 ? nb : 1) * device_cus();
     }
     return cap;
-}
-
-// The rescue vectors sit past both grid kernels' regions (grid_cg_workspace_floats).
-static size_t rescue_offset(int m, int C) {
-    const size_t Cp = size_t((C + 3) & ~3);
-    const size_t classic = 64 + size_t(3) * m * Cp + size_t(3) * kGCM * 1024;
-    const size_t gv = kSyncWords + size_t(2) * m * Cp + size_t(2) * kMaxG * 64;
-    return ((classic > gv ? classic : gv) + 63) & ~size_t(63);
 }
 
 // An ordinary launch sized within the co-resident capacity (one workgroup per CU at most, by
@@ -1195,7 +1113,9 @@ static hipError_t launch_persistent(F fn, int G, int nt, size_t lds, hipStream_t
 
 // ---- classic kernel: G workgroups of rows_per_wg rows
 template <class Mat, int LPR, int RPG>
-static hipError_t launch_grid(const Mat& A, GridCgArgs a, int G, float* ws, hipStream_t s) {
+static hipError_t launch_grid(const Mat& A, const GridSolve& c, int G, float* ws, hipStream_t s) {
+    GridCgArgs a{};
+    static_cast<GridSolve&>(a) = c;
     a.rows_per_wg = (a.m + G - 1) / G;
     G = (a.m + a.rows_per_wg - 1) / a.rows_per_wg;
     if (G > 1024 || G > coresident_capacity<Mat, LPR, RPG>())   // partials hold 1024 workgroups
@@ -1216,7 +1136,7 @@ static hipError_t launch_grid(const Mat& A, GridCgArgs a, int G, float* ws, hipS
 // the fewest rows per group that keep the grid within 64 workgroups (barrier cost grows with
 // the arrivals), else within the co-resident capacity (at most 1024, the partials buffer).
 template <class Mat>
-static hipError_t dispatch_classic(const Mat& A, const GridCgArgs& a, int64_t nnz, float* ws,
+static hipError_t dispatch_classic(const Mat& A, const GridSolve& a, int64_t nnz, float* ws,
                                    bool oversub, hipStream_t s) {
     const int64_t avg = a.m > 0 ? nnz / a.m : 0;
     const int LPR = avg <= 12 ? 4 : 8;
@@ -1254,13 +1174,19 @@ static hipError_t dispatch_classic(const Mat& A, const GridCgArgs& a, int64_t nn
     return hipErrorInvalidValue;
 }
 
-// ---- pipelined kernel
-template <class Mat, int NT, int LPR, int RPG, int MODE>
-static hipError_t launch_gv(const Mat& A, GvArgs a, int G, int64_t nnz, float* ws, bool zeroed,
-                            hipStream_t s) {
+// ---- cg_gv_kernel.  zeroed: the sync words are known zero (no memset)
+template <class Mat, int NT, int LPR, int RPG>
+static hipError_t launch_gv(const Mat& A, const GridSolve& c, int G, int64_t nnz, float* ws,
+                            bool zeroed, hipStream_t s) {
+    GvArgs a{};
+    static_cast<GridSolve&>(a) = c;
+    a.Cp = (a.C + 3) & ~3;
+    a.NQ = (a.C + 3) >> 2;
+    a.PW = 3 * a.C <= 32 ? 32 : 64;
+    a.hier = 1;   // XCD-class hierarchical arrivals (a flat counter measured 116 against 74 us)
     a.rows_per_wg = (a.m + G - 1) / G;
     G = (a.m + a.rows_per_wg - 1) / a.rows_per_wg;
-    auto fn = cg_gv_kernel<Mat, NT, LPR, RPG, MODE>;
+    auto fn = cg_gv_kernel<Mat, NT, LPR, RPG>;
     allow_full_lds(reinterpret_cast<const void*>(fn));
     // the slice: the workgroup's share of the entries with a quarter of margin (rows beyond it
     // read the CSR), within what the static LDS leaves; unknown nnz (< 0): all of it
@@ -1283,75 +1209,54 @@ static hipError_t launch_gv(const Mat& A, GvArgs a, int G, int64_t nnz, float* w
         if (e != hipSuccess) return e;
     }
     if (debug_log())
-        fprintf(stderr, "gll: grid CG (%s) G=%d rows/wg=%d NT=%d LPR=%d RPG=%d lds=%zu hier=%d\n",
-                MODE == 0 ? "pipelined" : "Chronopoulos-Gear", G, a.rows_per_wg, NT, LPR, RPG, lds,
-                a.hier);
+        fprintf(stderr, "gll: grid CG (Chronopoulos-Gear) G=%d rows/wg=%d NT=%d LPR=%d RPG=%d lds=%zu\n",
+                G, a.rows_per_wg, NT, LPR, RPG, lds);
     return launch_persistent(fn, G, NT, lds, s, "gridcg.hip:launch_gv", A, a);
 }
 
 // Workgroups: one per CU at most, about 16 rows each;
 // lanes per row as wide as the rows per workgroup allow; up to 512 rows per workgroup (m <=
 // 131,072 at 256 workgroups).  hipErrorNotSupported: no configuration holds it.
-template <class Mat, int MODE>
-static hipError_t dispatch_gv(const Mat& A, const GridCgArgs& c, int64_t nnz, float* ws,
-                              hipStream_t s) {
-    GvArgs a{};
-    a.m = c.m;
-    a.C = c.C;
-    a.Cp = (c.C + 3) & ~3;
-    a.NQ = (c.C + 3) >> 2;
-    a.PW = 3 * c.C <= 32 ? 32 : 64;
-    a.max_iter = c.max_iter;
-    a.rtol = c.rtol;
-    a.atol = c.atol;
-    a.b = c.b;
-    a.b_dtype = c.b_dtype;
-    a.out64 = c.out64;
-    a.out32 = c.out32;
-    a.diag_fail = c.diag_fail;
-    a.st_iters = c.st_iters;
-    a.st_nonconv = c.st_nonconv;
-    a.st_failed = c.st_failed;
-    a.st_rescued = c.st_rescued;
-    a.hier = 1;   // XCD-class hierarchical arrivals (a flat counter measured 116 against 74 us)
+template <class Mat>
+static hipError_t dispatch_gv(const Mat& A, const GridSolve& c, int64_t nnz, float* ws,
+                              bool zeroed, hipStream_t s) {
     int cap = std::min(kMaxG, device_cus());
     if (knob(GLL_KNOB_GRID_CAP) > 0) cap = std::min(cap, knob(GLL_KNOB_GRID_CAP));
-    int G = int(std::min<int64_t>(cap, (int64_t(a.m) + 15) / 16));
+    int G = int(std::min<int64_t>(cap, (int64_t(c.m) + 15) / 16));
     if (G < 1) G = 1;
-    const int R = (a.m + G - 1) / G;
+    const int R = (c.m + G - 1) / G;
     // 256 threads while lanes per row can stay >= 4 with one row per lane group; 1024 threads
     // (16 waves: more gathers in flight per CU) for long row blocks
     const int nt = R <= 64 ? 256 : 1024;
     if (nt == 256) {
-        if (R <= 16) return launch_gv<Mat, 256, 16, 1, MODE>(A, a, G, nnz, ws, c.sync_zeroed != 0, s);
-        if (R <= 32) return launch_gv<Mat, 256, 8, 1, MODE>(A, a, G, nnz, ws, c.sync_zeroed != 0, s);
-        if (R <= 64) return launch_gv<Mat, 256, 4, 1, MODE>(A, a, G, nnz, ws, c.sync_zeroed != 0, s);
-        if (R <= 128) return launch_gv<Mat, 256, 4, 2, MODE>(A, a, G, nnz, ws, c.sync_zeroed != 0, s);
-        if (R <= 256) return launch_gv<Mat, 256, 4, 4, MODE>(A, a, G, nnz, ws, c.sync_zeroed != 0, s);
+        if (R <= 16) return launch_gv<Mat, 256, 16, 1>(A, c, G, nnz, ws, zeroed, s);
+        if (R <= 32) return launch_gv<Mat, 256, 8, 1>(A, c, G, nnz, ws, zeroed, s);
+        if (R <= 64) return launch_gv<Mat, 256, 4, 1>(A, c, G, nnz, ws, zeroed, s);
+        if (R <= 128) return launch_gv<Mat, 256, 4, 2>(A, c, G, nnz, ws, zeroed, s);
+        if (R <= 256) return launch_gv<Mat, 256, 4, 4>(A, c, G, nnz, ws, zeroed, s);
     } else {
-        if (R <= 64) return launch_gv<Mat, 1024, 16, 1, MODE>(A, a, G, nnz, ws, c.sync_zeroed != 0, s);
-        if (R <= 128) return launch_gv<Mat, 1024, 8, 1, MODE>(A, a, G, nnz, ws, c.sync_zeroed != 0, s);
-        if (R <= 256) return launch_gv<Mat, 1024, 4, 1, MODE>(A, a, G, nnz, ws, c.sync_zeroed != 0, s);
-        if (R <= 512) return launch_gv<Mat, 1024, 4, 2, MODE>(A, a, G, nnz, ws, c.sync_zeroed != 0, s);
+        if (R <= 64) return launch_gv<Mat, 1024, 16, 1>(A, c, G, nnz, ws, zeroed, s);
+        if (R <= 128) return launch_gv<Mat, 1024, 8, 1>(A, c, G, nnz, ws, zeroed, s);
+        if (R <= 256) return launch_gv<Mat, 1024, 4, 1>(A, c, G, nnz, ws, zeroed, s);
+        if (R <= 512) return launch_gv<Mat, 1024, 4, 2>(A, c, G, nnz, ws, zeroed, s);
     }
     return hipErrorNotSupported;
 }
 
-// The pipelined kernel unless the oversubscription test asks for the classic sizing; past the
-// pipelined kernel's row capacity, the classic kernel.
+// cg_gv_kernel unless the oversubscription test asks for the classic sizing; past its row
+// capacity, the classic kernel.  (Chronopoulos-Gear for the Luu solves as for the general CSR:
+// the one-barrier form's extra recurrences let the true residual drift away from the recursive
+// one the stop test reads: at m = 2100 (22-24 iterations, rtol 1e-6) it returned
+// ||b - Luu x|| = 4.0-9.2e-6 ||b|| where textbook fp32 PCG and every other kernel reach
+// 1.0-1.2e-6, tests/test_gpu_cg_contract.py, profiles/cg01_gpu_tests.txt.)
 template <class Mat>
-static hipError_t dispatch_grid(const Mat& A, const GridCgArgs& a, int64_t nnz, float* ws,
-                                bool oversub, hipStream_t s) {
+static hipError_t dispatch_grid(const Mat& A, const GridSolve& c, int64_t nnz, float* ws,
+                                bool oversub, bool zeroed, hipStream_t s) {
     if (!oversub) {
-        // Chronopoulos-Gear for the Luu solves as for the general CSR.  The pipelined form's
-        // extra recurrences (w, z, s, q) let the true residual drift away from the recursive one
-        // the stop test reads: at m = 2100 (22-24 iterations, rtol 1e-6) it returned
-        // ||b - Luu x|| = 4.0-9.2e-6 ||b|| where textbook fp32 PCG and every other kernel reach
-        // 1.0-1.2e-6 (tests/test_gpu_cg_contract.py, profiles/cg01_gpu_tests.txt).
-        const hipError_t e = dispatch_gv<Mat, 1>(A, a, nnz, ws, s);
+        const hipError_t e = dispatch_gv(A, c, nnz, ws, zeroed, s);
         if (e != hipErrorNotSupported) return e;
     }
-    return dispatch_classic(A, a, nnz < 0 ? int64_t(a.m) * 8 : nnz, ws, oversub, s);
+    return dispatch_classic(A, c, nnz < 0 ? int64_t(c.m) * 8 : nnz, ws, oversub, s);
 }
 
 hipError_t launch_cg_grid_luu(const Layout& L, void* wsp, const void* b, int b_dtype,
@@ -1362,7 +1267,7 @@ hipError_t launch_cg_grid_luu(const Layout& L, void* wsp, const void* b, int b_d
     LuuRows A{L.at<int32_t>(wsp, L.row_start), L.at<int32_t>(wsp, L.row_len),
               L.at<int32_t>(wsp, L.ucnt),      L.at<int32_t>(wsp, L.col),
               L.at<float>(wsp, L.w),           L.at<float>(wsp, L.diag), L.base};
-    GridCgArgs a{};
+    GridSolve a{};
     a.m = L.m;
     a.C = L.C;
     a.max_iter = max_iter;
@@ -1378,11 +1283,11 @@ hipError_t launch_cg_grid_luu(const Layout& L, void* wsp, const void* b, int b_d
     // the public words are one array (include/gll.h): GLL_ST_GRID_RESCUED beside SOLVE_FAILED
     a.st_rescued = st_failed ? st_failed - GLL_ST_SOLVE_FAILED + GLL_ST_GRID_RESCUED : nullptr;
     a.diag_fail = (L.flags & GLL_FLAG_DIAG_GRID_FAIL) ? 1 : 0;
-    a.sync_zeroed = 1;   // row_build zeroed them before the forward; every solve leaves them so
     // U-block entries per row ~ 1.5 (K-1) m / n on kNN graphs (union rows, U share)
     const int64_t nnz_est = int64_t(double(L.m) * (L.K - 1) * 1.5 * double(L.m) / double(L.n)) + L.m;
+    // sync words: row_build zeroed them before the forward; every solve leaves them so
     return dispatch_grid(A, a, nnz_est, L.at<float>(wsp, L.cgv),
-                         (L.flags & GLL_FLAG_DIAG_GRID_OVERSUB) != 0, s);
+                         (L.flags & GLL_FLAG_DIAG_GRID_OVERSUB) != 0, true, s);
 }
 
 hipError_t launch_cg_grid_csr(int m, int C, const int32_t* row_ptr, const int32_t* col,
@@ -1391,7 +1296,7 @@ hipError_t launch_cg_grid_csr(int m, int C, const int32_t* row_ptr, const int32_
                               int32_t* failed, float* ws, hipStream_t s) {
     if (C > kGCM) return hipErrorNotSupported;
     CsrRows A{row_ptr, col, val};
-    GridCgArgs a{};
+    GridSolve a{};
     a.m = m;
     a.C = C;
     a.max_iter = max_iter;
@@ -1404,7 +1309,7 @@ hipError_t launch_cg_grid_csr(int m, int C, const int32_t* row_ptr, const int32_
     a.st_nonconv = nonconv;
     a.st_failed = failed;
     a.st_rescued = failed ? failed - GLL_ST_SOLVE_FAILED + GLL_ST_GRID_RESCUED : nullptr;
-    return dispatch_grid(A, a, nnz, ws, false, s);
+    return dispatch_grid(A, a, nnz, ws, false, false, s);
 }
 
 }  // namespace gll

@@ -14,6 +14,7 @@
 //   * W_ij = exp(-4 d_ij^2 / (eps_i eps_j)) (GLL.py:216/233), degree, and for unlabeled rows
 //     the Luu diagonal deg + tau, the U-block length, and rhs = W_ul Y (= -Lul Y, GLL.py:53);
 //     labeled rows write P = Y and w = 0 for the backward (GLL.py:104,109).
+#include "cg_route.h"   // grid_cg_route
 #include "gll_internal.h"
 
 namespace gll {
@@ -66,7 +67,7 @@ struct RowArgs {
     int SE, m;
     char* vr;           // [m][VRM] packed virtual rows of the balanced CG (VRM = 0: none)
     int VRM;
-    unsigned* fsync;    // fused backward counters (solve.hip cg_grad_fused_kernel): zeroed here
+    unsigned* fsync;    // fused backward counters (fused_bwd.hip cg_grad_fused_kernel): zeroed here
     unsigned* gsync;    // whole-GPU CG sync words (gridcg.hip), zeroed here; null: not used
     size_t wss;   // batched launches: workspace stride between graphs (bytes)
 

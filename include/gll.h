@@ -118,7 +118,7 @@ extern "C" {
 #define GLL_KNOB_ROW_PRE 5    /* row build label prefetch: 1 on, 2 off (rows.hip) */
 #define GLL_KNOB_GRAD_SPLIT 6 /* fused backward: long rows in feature parts: 0 automatic (on where
                                * a row holds more than one f32x4 per lane, d > 256), 1 the same,
-                               * 2 off: the launch of one wave per row (solve.hip) */
+                               * 2 off: the launch of one wave per row (fused_bwd.hip) */
 #define GLL_KNOB_COUNT 7
 int gll_set_knob(int knob, int value);
 
@@ -466,6 +466,20 @@ int gll_select_route(const gll_problem* p, int B, int x_aligned, int rows,
 #define GLL_FUSED_PLAN_WORDS 8
 int gll_fused_plan(const gll_problem* p, int x_aligned, int capacity,
                    int32_t out[GLL_FUSED_PLAN_WORDS]);
+
+/* Diagnostic: which kernel solves the Luu systems of this problem in a launch over B graphs (the
+ * forward solve, and the backward's when it runs unfused).  No HIP call: it runs without a GPU,
+ * and the launcher launches from the same route (cg_route.h cg_route, solve.hip's table).
+ * out[0] = 1 when the whole-GPU CG (cg_gv_kernel, gridcg.hip) is tried first; out[1..5] = the
+ * per-column variant the solve takes -- or falls back to when no grid configuration holds the
+ * system: family (0 cg_ell_kernel, 1 cg_vr_kernel, 2 cg_lds_kernel), threads NT, rows per thread
+ * R, register ELL slots S (cg_ell) or virtual rows per thread RV (cg_vr), MODE (cg_ell: 3 the
+ * Neumann-1 preconditioner, 1 Jacobi; cg_vr 1; cg_lds 0, classic PCG with Jacobi); out[6] = 1 when
+ * cg_lds keeps its vectors in LDS; out[7] = that variant's row in the table of instantiated
+ * kernels (-1, and GLL_ERR_UNSUPPORTED, when it has none: the launch would fail), out[8] = the
+ * table's length.  Reads GLL_KNOB_VR_RV. */
+#define GLL_CG_ROUTE_WORDS 9
+int gll_cg_route(const gll_problem* p, int B, int32_t out[GLL_CG_ROUTE_WORDS]);
 
 /* Build identity: sha256 (16 hex) of the sources, headers and flags this library was built
  * from (graphlearninglayer_amd/build.py source_digest).  bench.py cites only profiles

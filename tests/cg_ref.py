@@ -20,8 +20,10 @@ Preconditioners (A = D - N, D the diagonal):
 
 `luu_from_view` assembles Luu and the right-hand-side operator W_ul from the arrays a workspace
 holds (gll_workspace_view), so the matrix under test is the GPU's own fp32 graph.  `route` restates
-the host-side kernel choice of solve.hip cg_dispatch, gll_internal.h vr_threads / grid_cg_route and
-api.hip backward_impl / gll_cg_csr, so a test can say which kernel a problem runs.
+the host-side kernel choice of cg_route.h cg_route / grid_cg_route, gll_internal.h vr_threads and
+api.hip backward_impl / gll_cg_csr, so a test can say which kernel a problem runs.  It stays an
+independent restatement: `lib_route` asks the library itself (gll_cg_route), and the tests hold
+the two against each other.
 """
 from __future__ import annotations
 
@@ -143,7 +145,8 @@ def luu_from_view(row_start, row_len, col, w, deg, tau, base):
 # Which kernel solves a problem: the host-side choice of the library, restated.
 # ------------------------------------------------------------------------------------------
 FLAG_CG_GRID, FLAG_CG_PERCOL, FLAG_CG_ELL, FLAG_CG_VR, FLAG_BWD_UNFUSED = 1, 8, 512, 1024, 16384
-LDS_DYN = 159 * 1024   # solve.hip kLdsDyn: the dynamic share of the 160 KiB
+LDS_DYN = 159 * 1024   # cg_route.h kLdsDyn: the dynamic share of the 160 KiB
+D_FEAT_DEFAULT = 16    # the route does not depend on d
 
 
 def vr_threads(n, m, K, flags, knob_rv=0):
@@ -160,7 +163,7 @@ def vr_threads(n, m, K, flags, knob_rv=0):
 
 
 def route(n, base, C, K, flags=0, B=1, knob_rv=0):
-    """(kernel, preconditioner) of a Luu solve (solve.hip cg_dispatch; the adjoint of a single
+    """(kernel, preconditioner) of a Luu solve (cg_route.h cg_route; the adjoint of a single
     graph with fixed eps takes the same choice inside cg_grad_fused_kernel unless
     GLL_FLAG_BWD_UNFUSED or the shape sends it to the two-launch path).  The whole-GPU kernel is
     named when grid_cg_route holds; a system past its capacity falls through at run time."""
@@ -188,6 +191,32 @@ def route(n, base, C, K, flags=0, B=1, knob_rv=0):
     if m <= 4096:
         return "cg_ell<1024,4,4>", "jacobi"
     return ("cg_lds<lds>" if 64 * 4 + 5 * m * 4 <= LDS_DYN else "cg_lds<global>"), "jacobi"
+
+
+def lib_route(n, base, C, K, flags=0, B=1, knob_rv=0, d=D_FEAT_DEFAULT):
+    """The library's own choice for the same problem, in route()'s words: gll_cg_route (no GPU)
+    decoded to (kernel, preconditioner), plus its raw words.  Sets and restores GLL_KNOB_VR_RV."""
+    import ctypes as ct
+
+    from graphlearninglayer_amd import GLL as G
+    from graphlearninglayer_amd import _lib
+    p = G.make_problem(n, d, base, C, K, 0.07, 1.0, flags=flags)
+    out = (ct.c_int32 * 9)()
+    _lib.set_knob(_lib.KNOB_VR_RV, knob_rv)
+    try:
+        rc = _lib.lib().gll_cg_route(ct.byref(p), B, out)
+    finally:
+        _lib.set_knob(_lib.KNOB_VR_RV, 0)
+    grid_first, family, NT, R, S, MODE, vec_in_lds, row, rows = list(out)
+    if grid_first:
+        name = "cg_gv", "jacobi"
+    elif family == 0:
+        name = f"cg_ell<{NT},{R},{S}>", "neumann" if MODE == 3 else "jacobi"
+    elif family == 1:
+        name = f"cg_vr<{NT},{R},{S}>", "jacobi"
+    else:
+        name = ("cg_lds<lds>" if vec_in_lds else "cg_lds<global>"), "jacobi"
+    return rc, name, list(out)
 
 
 def csr_route(m, C):

@@ -46,7 +46,7 @@ numpy float32 with the edges of each row in a random order and records how much 
 uses (0.004-0.08: 13 x slack or more, while the bound still sits below 2e-5 of max|grad| on
 ordinary rows, against the suite's 1e-4).
 
-`route` restates the host-side choice of the backward (api.hip backward_impl, solve.hip
+`route` restates the host-side choice of the backward (api.hip backward_impl, fused_bwd.hip
 launch_cg_grad_fused, grad.hip launch_backward_grad / grad_use_chunks / grad_nd / grad_chunked) in
 the style of cg_ref.route: which kernel instantiations run and how many launches of each
 (GLL_K_EDGE, GLL_K_GRAD, GLL_K_BWD, GLL_K_CG) a backward makes.  The one gate it cannot restate is

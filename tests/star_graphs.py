@@ -75,7 +75,7 @@ def row_lengths(X: np.ndarray, k: int) -> np.ndarray:
 
 
 def row_parts(length: int, nd: int) -> int:
-    """Parts the fused backward runs a row of `length` edges in (solve.hip row_parts): the fewest
+    """Parts the fused backward runs a row of `length` edges in (fused_bwd.hip row_parts): the fewest
     of 1, 2, 4 whose EB P slots hold its first 64 edges; rows of one f32x4 per lane stay whole."""
     eb, pmax = (16 if nd <= 2 else 8), (4 if nd >= 2 else 1)
     p = 1

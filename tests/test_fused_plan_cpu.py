@@ -1,4 +1,4 @@
-"""Host sizing of the fused backward's launch (solve.hip fused_grid through gll_fused_plan): the
+"""Host sizing of the fused backward's launch (fused_bwd.hip fused_grid through gll_fused_plan): the
 grid, the spare gradient waves that take the parts of long rows, and the LDS -- no GPU needed, the
 co-resident capacity is an argument."""
 import ctypes as ct

@@ -289,11 +289,16 @@ ALL_FORWARD = R.FORWARD_CASES + (R.RESCUE_CASE,)
 
 
 def _kernel_ran(case, st, ncg):
-    """The intended kernel: the restated host-side choice names it, exactly one CG launch was
-    bracketed per forward, and the whole-GPU route was (or, injected, was not) left alone."""
+    """The intended kernel: the restated host-side choice names it, and so does the library's own
+    route for the case's problem (gll_cg_route: what cg_dispatch launches from); exactly one CG
+    launch was bracketed per forward, and the whole-GPU route was (or, injected, was not) left
+    alone."""
     L = _lib()
     assert R.route(case.n, case.base, case.C, case.k, case.flags, case.B, case.knob_rv) == \
         (case.kernel, case.precond)
+    rc, name, words = R.lib_route(case.n, case.base, case.C, case.k, case.flags, case.B,
+                                  case.knob_rv)
+    assert rc == 0 and name == (case.kernel, case.precond), (rc, name, words)
     assert ncg == 1, ncg
     rescued = sum(s[L.ST_GRID_RESCUED] for s in st)
     assert rescued == (1 if case.flags & R.FLAG_DIAG_GRID_FAIL else 0)

@@ -1,4 +1,4 @@
-"""The fused backward's row parts (solve.hip cg_grad_fused_kernel): rows of more
+"""The fused backward's row parts (fused_bwd.hip cg_grad_fused_kernel): rows of more
 than EB edges run as 2 or 4 waves, each over a part of the row's features.  (run on the MI355X:
 -m gpu)
 

@@ -1376,7 +1376,7 @@ def _fwd_bwds_c_abi(X, Y, k, tau, eps, gbar, flags=0, backward_calls=1, counts=F
 
 @pytest.mark.parametrize("cfg", ["plumbing", "ns", "wide_base"])
 def test_fused_backward_equals_two_launches_bitwise(cfg):
-    """The fused backward (adjoint CG + feature gradient in one launch, solve.hip
+    """The fused backward (adjoint CG + feature gradient in one launch, fused_bwd.hip
     cg_grad_fused_kernel: single small graphs, fixed eps) against the same two kernels as two
     launches (GLL_FLAG_BWD_UNFUSED): bitwise equal, and equal again on a second backward over
     the same workspace (the hand-off counters re-arm); against the float64 oracle at 1e-4.

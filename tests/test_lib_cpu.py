@@ -221,6 +221,45 @@ def test_product_library_reads_no_switch_but_debug():
     assert names == ["GLL_DEBUG"], names
 
 
+def test_cg_route_table_is_complete_and_minimal():
+    """The per-column CG launches through a table of instantiated variants (solve.hip) from the
+    route cg_route (cg_route.h) computes; gll_cg_route reports that route without a GPU.  Every
+    contract case (tests/cg_ref.py) decodes to the kernel and preconditioner its label names, and
+    over the sweep the library's route equals the independent restatement cg_ref.route, every
+    reachable route has a table row, and every table row is reached."""
+    import itertools
+
+    from tests import cg_ref as R
+    for case in (*R.FORWARD_CASES, R.RESCUE_CASE):
+        rc, name, words = R.lib_route(case.n, case.base, case.C, case.k, case.flags, case.B,
+                                      case.knob_rv)
+        assert rc == 0 and name == (case.kernel, case.precond), (case.name, rc, name, words)
+    reached, length, count = set(), None, 0
+    for m, base, B, C, k, flags, rv in itertools.product(
+            (1, 64, 65, 128, 129, 256, 257, 512, 513, 1024, 1025, 1536, 1537, 2048, 2049, 4096,
+             4097, 8200),
+            (250, 300, 2400), (1, 2, 26, 27), (1, 10, 16, 17), (10, 25),
+            (0, R.FLAG_CG_GRID, R.FLAG_CG_PERCOL, R.FLAG_CG_ELL, R.FLAG_CG_VR), (0, 4)):
+        n = base + m
+        rc, name, words = R.lib_route(n, base, C, k, flags, B, rv)
+        assert rc == 0 and words[7] >= 0, (m, base, B, C, k, flags, rv, rc, words)
+        assert name == R.route(n, base, C, k, flags, B, rv), (m, base, B, C, k, flags, rv, words)
+        count += 1
+        length = words[8]
+        reached.add(words[7])
+    assert count == 18 * 3 * 4 * 4 * 2 * 5 * 2
+    # The sweep's bases (250 and up) keep the U share of a row small, so it never asks for 8 or 10
+    # virtual rows per thread at one row per thread, nor for 10 at two or three: four more
+    # problems (m, base, k) with almost no labelled rows, or m = 1,250, reach those rows.
+    for (m, base, k), want in (((512, 10, 25), "cg_vr<512,1,8>"), ((512, 10, 50), "cg_vr<512,1,10>"),
+                               ((1024, 10, 25), "cg_vr<512,2,10>"),
+                               ((1250, 250, 25), "cg_vr<512,3,10>")):
+        rc, name, words = R.lib_route(base + m, base, 10, k)
+        assert rc == 0 and name == (want, "jacobi") == R.route(base + m, base, 10, k), (m, words)
+        reached.add(words[7])
+    assert reached == set(range(length)), sorted(set(range(length)) - reached)
+
+
 def test_select_route_table_is_complete_and_minimal():
     """The kNN select launches through a table of instantiated variants (select.hip); a variant
     select_route (knn_route.h) can return and the table lacks is a launch that fails, and a row

@@ -5,7 +5,7 @@ Loads the timestamp build (tools/libgll_trace.so.trace, a copy of _obj/libgll_tr
 backward through the C ABI and reads, per gradient wave of cg_grad_fused_kernel, the
 s_memrealtime (100 MHz) stamps of: release seen, w loaded (+ first coefficients), products done,
 stored; plus the row, its length and the wave's CU / XCC.  A row may run as several waves (parts
-of its feature range, solve.hip): a row's times are those of its last part to store.  Prints the
+of its feature range, fused_bwd.hip): a row's times are those of its last part to store.  Prints the
 distribution of each phase after the release, the slowest rows, the maximum stored time by row
 length, and the adjoint solves' last exit (which the gradient waves' polling must not move).
 
@@ -52,7 +52,7 @@ U = torch.empty(n - base, 10, dtype=torch.float64, device=dev)
 gx = torch.empty(n, d, dtype=torch.float32, device=dev)
 s = ct.c_void_p(torch.cuda.current_stream().cuda_stream)
 vp = ct.c_void_p
-EB = 16 if d <= 512 else 8   # neighbour rows a whole-row wave holds (solve.hip)
+EB = 16 if d <= 512 else 8   # neighbour rows a whole-row wave holds (fused_bwd.hip)
 BINS = [(0, 16), (17, 32), (33, 64), (65, 1 << 30)]
 
 
@@ -141,7 +141,7 @@ for rep in range(5):
     tails.append(tail)
     print(f"  tail (max stored over all rows - max stored over rows of <= 16 edges): {tail:.2f}")
     buf = (ct.c_ulonglong * 64)()
-    lib.gll_trace_read(2, buf)
+    lib.gll_trace_read(6, buf)   # trace unit 6: fused_bwd.hip
     fz = np.array(buf[:], dtype=np.uint64).astype(np.int64)
     if fz[16] and 0 < fz[32] < 2 ** 62:
         print(f"  us from the first CG entry: last CG exit +{0.01 * (fz[33] - fz[32]):.2f}, first "

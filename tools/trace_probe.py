@@ -25,10 +25,11 @@ lib = ct.CDLL(_tl if os.path.exists(_tl) else
 lib.gll_workspace_bytes.restype = ct.c_size_t
 lib.gll_trace_read.argtypes = [ct.c_int, ct.POINTER(ct.c_ulonglong)]
 # unit -> (name, kernels by GLL_TRACE_SCOPE index; "" = an index the unit does not use).  Unit 0 is
-# gram.hip (it keeps the symbols of the former knn unit), unit 5 select.hip.
+# gram.hip (it keeps the symbols of the former knn unit), unit 5 select.hip, unit 6 fused_bwd.hip
+# (the fused backward: its gradient checkpoints and the cg_ell_body checkpoints of its CG role).
 UNITS = {0: ("knn", ["gram", "", "gram_wide", "gram48", "gram_bf3"]), 1: ("rows", ["row_build"]),
          2: ("solve", ["cg_ell", "cg_lds", "cg_csr"]), 3: ("grad", ["edge_coef", "grad_spmm"]),
-         5: ("select", ["", "select"])}
+         5: ("select", ["", "select"]), 6: ("fused", ["cg_grad_fused"])}
 CG_PTS = ["entry", "ell loaded+P", "ovf compacted", "rz/bb reduced", "it1 spmv", "it1 pAp",
           "it1 rr", "it1 P published", "loop done", "stored"]
 
@@ -116,23 +117,25 @@ def timeline(tr, label):
               f"+{TICK_US * (rw[23] - rw[10]):.2f}")
     if rw[20] or rw[21]:
         print(f"row_build longest wave: every 16th row {TICK_US * rw[20]:.2f} us, hub rows {TICK_US * rw[21]:.2f} us")
-    cyc = tr[2][10:16].astype(np.int64)
-    if cyc[0] and cyc[5]:
-        lab = ["update+store", "publish barrier", "spmv+dots", "reduce (dpp+lds+barrier)", "alpha/beta+p,s"]
-        print("cg block 0 wave 0, iteration 3 (shader cycles): " +
-              ", ".join(f"{lab[q]} {cyc[q + 1] - cyc[q]}" for q in range(5)) +
-              f" | total {cyc[5] - cyc[0]}")
-    fz = tr[2].astype(np.int64)
+    for u, who in ((2, "cg"), (6, "fused backward's cg")):
+        cyc = tr[u][10:16].astype(np.int64)
+        if cyc[0] and cyc[5]:
+            lab = ["update+store", "publish barrier", "spmv+dots", "reduce (dpp+lds+barrier)", "alpha/beta+p,s"]
+            print(f"{who} block 0 wave 0, iteration 3 (shader cycles): " +
+                  ", ".join(f"{lab[q]} {cyc[q + 1] - cyc[q]}" for q in range(5)) +
+                  f" | total {cyc[5] - cyc[0]}")
+    fz = tr[6].astype(np.int64)
     if fz[16] and fz[32] and fz[32] < 2 ** 62:
-        base = fz[32]   # first entry of the solve kernel (the CG role of the fused backward)
+        base = fz[32]   # first entry of the CG role of the fused backward
         print("fused backward (us from the first CG entry): " + ", ".join(
             f"{nm} +{TICK_US * (fz[q] - base):.2f}" for q, nm in
             [(16, "grad block C prefetch issued"), (17, "its wait over"), (18, "its rows stored"),
              (33, "last CG exit"), (19, "last grad exit")] if fz[q]))
-    pts = tr[2][:10].astype(np.int64)
-    if pts[0]:
-        print("cg block 0: " + ", ".join(f"{CG_PTS[i]} +{TICK_US * (pts[i] - pts[0]):.2f}"
-                                         for i in range(1, 10) if pts[i]))
+    for u, who in ((2, "cg"), (6, "fused backward's cg")):
+        pts = tr[u][:10].astype(np.int64)
+        if pts[0]:
+            print(f"{who} block 0: " + ", ".join(f"{CG_PTS[i]} +{TICK_US * (pts[i] - pts[0]):.2f}"
+                                                for i in range(1, 10) if pts[i]))
 
 
 for _ in range(10):
