@@ -864,24 +864,71 @@ def _knn_query_device(Xq32, Xdb32, k, flags, status, dev):
     return idx, d2
 
 
+def _check_candidates(cand, Q, lo, what, name):
+    """Caller-supplied candidates of the query calls: an integer tensor Q x c, lo <= c <=
+    _lib.RERANK_MAX_C.  Metadata alone: no GPU call, no host sync."""
+    if not torch.is_tensor(cand):
+        raise TypeError(f"{what}: {name} must be a Tensor")
+    if cand.is_floating_point() or cand.is_complex() or cand.dtype == torch.bool:
+        raise ValueError(f"{what}: {name} must hold integers (int32 or int64)")
+    if cand.dim() != 2 or cand.shape[0] != Q or not lo <= cand.shape[1] <= _lib.RERANK_MAX_C:
+        raise ValueError(f"{what}: {name} must be Q x c = {Q} x c with {lo} <= c <= "
+                         f"{_lib.RERANK_MAX_C}, got {tuple(cand.shape)}")
+
+
+def _knn_rerank_device(Xq32, Xdb32, cand, k, flags, status, dev):
+    """gll_knn_rerank on prepared fp32 device rows and the caller's candidates (narrowed to int32
+    as the layer's neighbors are): (idx int32 Q x k, d2 float32 Q x k)."""
+    Q, d = Xq32.shape
+    N = Xdb32.shape[0]
+    c32 = cand.detach().to(device=dev, dtype=torch.int32).contiguous()
+    idx = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    d2 = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().gll_knn_rerank(Q, N, d, c32.shape[1], k, flags, Xq32.data_ptr(),
+                                         Xdb32.data_ptr(), c32.data_ptr(), idx.data_ptr(),
+                                         d2.data_ptr(), status.data_ptr(), _stream(dev)),
+               "gll_knn_rerank")
+    return idx, d2
+
+
 def knn_query(Xq: torch.Tensor, Xdb: torch.Tensor, k: int, flags: int = 0,
-              return_status: bool = False):
+              return_status: bool = False, candidates=None, keep_order: bool = False):
     """idx, d2 = knn_query(Xq, Xdb, k): for every row of Xq (Q x d) the k rows of Xdb (N x d) with
     the smallest float64 sum_f (q_f - x_f)^2 of the fp32 features, equal distances to the lower
     index -- exact, like the graph build's kNN.  idx int64 Q x k, d2 float32 Q x k (the fp32
     difference-form distances), each list ordered by (d2, idx), on Xdb's device.  float16 /
     bfloat16 / float64 features are converted to float32 first.  flags: _lib.QF_SMALL_PANELS.
-    return_status=True adds the 4 int32 status words of the call (_lib.QST_*, a device tensor)."""
+    return_status=True adds the 4 int32 status words of the call (_lib.QST_*, a device tensor).
+    candidates: an integer tensor Q x c (any device), k <= c <= 512 -- no search: one launch
+    (gll_knn_rerank) picks each row's k nearest among its own candidates, with the search's
+    distance bits; entries outside [0, N) and repeats are never chosen, and a row with fewer than
+    k valid ones ends in (-1, +inf) and is counted in status[_lib.QST_SHORT_ROW].
+    keep_order=True (c == k): the lists as they are, in the caller's order, with their distances
+    (+inf for an index outside [0, N))."""
     _check_query(Xq, Xdb, k, "knn_query")
     k, flags = int(k), int(flags)
     if flags & ~_lib.QF_SMALL_PANELS:
         raise ValueError(f"knn_query: unknown flags {flags}")
+    if candidates is None:
+        if keep_order:
+            raise ValueError("knn_query: keep_order needs candidates")
+    else:
+        _check_candidates(candidates, Xq.shape[0], k, "knn_query", "candidates")
+        if keep_order and candidates.shape[1] != k:
+            raise ValueError(f"knn_query: keep_order needs candidates of k = {k} columns, got "
+                             f"{candidates.shape[1]}")
+        if flags:
+            raise ValueError("knn_query: flags steer the search; candidates take none")
     dev = _device_for(Xdb)
     with torch.cuda.device(dev):
         status = torch.zeros(_lib.QST_NWORDS, dtype=torch.int32, device=dev)
         if Xq.shape[0] == 0:
             idx = torch.empty((0, k), dtype=torch.int64, device=dev)
             d2 = torch.empty((0, k), dtype=torch.float32, device=dev)
+        elif candidates is not None:
+            idx32, d2 = _knn_rerank_device(_features(Xq, dev), _features(Xdb, dev), candidates, k,
+                                           _lib.RR_KEEP_ORDER if keep_order else 0, status, dev)
+            idx = idx32.long()
         else:
             idx32, d2 = _knn_query_device(_features(Xq, dev), _features(Xdb, dev), k, flags,
                                           status, dev)
@@ -890,7 +937,7 @@ def knn_query(Xq: torch.Tensor, Xdb: torch.Tensor, k: int, flags: int = 0,
 
 
 def extend(Xq: torch.Tensor, Xdb: torch.Tensor, P: torch.Tensor, k: int = DEFAULT_K,
-           epsilon="auto", eps_db=None, return_status: bool = False):
+           epsilon="auto", eps_db=None, return_status: bool = False, neighbors=None):
     """Uq, labels = extend(Xq, Xdb, P, k): the harmonic (Nadaraya-Watson) out-of-sample extension
     of a solved graph, u(q) = sum_j w_qj P_j / sum_j w_qj over q's k - 1 nearest rows of Xdb
     (k has the layer's meaning, neighbours including the point itself; a query is not in the
@@ -901,7 +948,14 @@ def extend(Xq: torch.Tensor, Xdb: torch.Tensor, P: torch.Tensor, k: int = DEFAUL
     Differentiable: with grad mode on and Xq, Xdb, P or a one-element tensor epsilon requiring
     grad, Uq carries a grad_fn (gll_extend_backward: the neighbour lists frozen, as the layer's
     graph is; gradients in each input's dtype).  eps_db is a constant of the fitted graph and
-    never gets a gradient; labels are not differentiable."""
+    never gets a gradient; labels are not differentiable.
+    neighbors: an integer tensor Q x c (any device), k - 1 <= c <= 512, in place of the search:
+    re-rank + extension, two launches.  c == k - 1: each row's list as it is, in the caller's order
+    (the last column gives 'auto' its eps_q, as knn_ind[:, -1] does for the layer); c > k - 1: a
+    pool, of which every call takes the k - 1 nearest -- what the search gives while the pool
+    still holds them.  The backward runs on the re-ranked lists, frozen.  An index outside [0, N)
+    in a list, or a pool row with fewer than k - 1 valid entries (status[_lib.QST_SHORT_ROW]),
+    makes its row NaN."""
     if not isinstance(k, (int, np.integer)) or not 2 <= k <= MAX_K:
         raise ValueError(f"extend: k = {k}, need 2 <= k <= {MAX_K} (neighbours incl. self)")
     _check_query(Xq, Xdb, int(k) - 1, "extend")
@@ -918,19 +972,23 @@ def extend(Xq: torch.Tensor, Xdb: torch.Tensor, P: torch.Tensor, k: int = DEFAUL
         if not torch.is_tensor(eps_db) or eps_db.numel() != N:
             raise ValueError(f"extend: eps_db must hold N = {N} values")
     kn = int(k) - 1
-    dev = _device_for(Xdb)
     Q = Xq.shape[0]
+    if neighbors is not None:
+        _check_candidates(neighbors, Q, kn, "extend", "neighbors")
+    dev = _device_for(Xdb)
     eps_t = epsilon if torch.is_tensor(epsilon) else None
     if Q > 0 and torch.is_grad_enabled() and any(
             t is not None and t.requires_grad for t in (Xq, Xdb, P, eps_t)):
-        Uq, labels, status = _Extend.apply(Xq, Xdb, P, eps_t, kn, eps, eps_db, dev)
+        Uq, labels, status = _Extend.apply(Xq, Xdb, P, eps_t, kn, eps, eps_db, dev, neighbors)
     else:
-        Uq, labels, status = _extend_forward(Xq, Xdb, P, kn, eps, eps_db, dev)[:3]
+        Uq, labels, status = _extend_forward(Xq, Xdb, P, kn, eps, eps_db, dev, neighbors)[:3]
     return (Uq, labels, status) if return_status else (Uq, labels)
 
 
-def _extend_forward(Xq, Xdb, P, kn, eps, eps_db, dev):
-    """gll_knn_query + gll_extend: (Uq, labels, status) and what the backward reads."""
+def _extend_forward(Xq, Xdb, P, kn, eps, eps_db, dev, neighbors=None):
+    """gll_knn_query (or, on the caller's neighbors, gll_knn_rerank: a list of kn columns as it is,
+    the kn nearest of a wider pool) + gll_extend: (Uq, labels, status) and what the backward
+    reads."""
     Q, N, C = Xq.shape[0], Xdb.shape[0], P.shape[1]
     with torch.cuda.device(dev):
         status = torch.zeros(_lib.QST_NWORDS, dtype=torch.int32, device=dev)
@@ -943,7 +1001,12 @@ def _extend_forward(Xq, Xdb, P, kn, eps, eps_db, dev):
             if eps == 0.0:
                 e32 = eps_db.detach().to(device=dev, dtype=torch.float32).contiguous().view(-1)
             Xq32, Xdb32 = _features(Xq, dev), _features(Xdb, dev)
-            idx, d2 = _knn_query_device(Xq32, Xdb32, kn, 0, status, dev)
+            if neighbors is None:
+                idx, d2 = _knn_query_device(Xq32, Xdb32, kn, 0, status, dev)
+            else:
+                idx, d2 = _knn_rerank_device(
+                    Xq32, Xdb32, neighbors, kn,
+                    _lib.RR_KEEP_ORDER if neighbors.shape[1] == kn else 0, status, dev)
             _lib.check(_lib.lib().gll_extend(
                 Q, N, kn, C, idx.data_ptr(), d2.data_ptr(), P32.data_ptr(),
                 None if e32 is None else e32.data_ptr(), ct.c_float(eps), Uq.data_ptr(),
@@ -985,8 +1048,8 @@ class _Extend(torch.autograd.Function):
     lists are frozen, eps_db is a constant, labels and status carry no gradient."""
 
     @staticmethod
-    def forward(ctx, Xq, Xdb, P, eps_t, kn, eps, eps_db, dev):
-        Uq, labels, status, saved = _extend_forward(Xq, Xdb, P, kn, eps, eps_db, dev)
+    def forward(ctx, Xq, Xdb, P, eps_t, kn, eps, eps_db, dev, neighbors=None):
+        Uq, labels, status, saved = _extend_forward(Xq, Xdb, P, kn, eps, eps_db, dev, neighbors)
         ctx.save_for_backward(*saved)   # (Uq is recomputed by the kernel, bit for bit)
         ctx.eps = eps
         ctx.like = tuple(None if t is None else (t.dtype, t.device, t.shape)
@@ -1002,7 +1065,7 @@ class _Extend(torch.autograd.Function):
         what = ((_lib.EG_XQ if need[0] else 0) | (_lib.EG_XDB if need[1] else 0) |
                 (_lib.EG_P if need[2] else 0) | (_lib.EG_EPS if need[3] else 0))
         if what == 0:
-            return (None,) * 8
+            return (None,) * 9
         dev = Xdb32.device
         with torch.cuda.device(dev):
             g64 = gU.detach().to(device=dev, dtype=torch.float64).contiguous()
@@ -1014,7 +1077,7 @@ class _Extend(torch.autograd.Function):
             dtype, device, shape = like
             return g.to(device=device, dtype=dtype).reshape(shape)
 
-        return tuple(back(g, like) for g, like in zip(outs, ctx.like)) + (None,) * 4
+        return tuple(back(g, like) for g, like in zip(outs, ctx.like)) + (None,) * 5
 
 
 def extend_torch(Xq, Xdb, P, idx, epsilon="auto", eps_db=None):

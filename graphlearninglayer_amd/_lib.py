@@ -61,6 +61,9 @@ QUERY_MAX_K, QUERY_MAX_C = 256, 256   # gll_knn_query k / gll_extend kn and C
 QUERY_MAX_N = (2**31 - 1) // 2
 QST_RESCAN, QST_NONFINITE, QST_ZERO_SUM = 0, 1, 2   # gll_knn_query / gll_extend status words
 QST_NWORDS = 4
+RR_KEEP_ORDER = 1                # gll_knn_rerank flag: list mode, the caller's order kept (c == k)
+RERANK_MAX_C = 512               # gll_knn_rerank: candidates per row (the wave's slots)
+QST_SHORT_ROW = 3                # gll_knn_rerank: pool rows with fewer than k valid candidates
 EG_XQ, EG_XDB, EG_P, EG_EPS = 1, 2, 4, 8   # gll_extend_backward `what` bits
 EGF_SMALL_LISTS = 1              # gll_extend_backward flag: 64-entry in-LDS lists (tests: the long-list path)
 EGST_ZERO_SUM, EGST_LONG_LIST = 2, 3   # gll_extend_backward status words
@@ -92,7 +95,7 @@ EXPORTS = (
     "gll_supcon_scratch_bytes", "gll_supcon_forward", "gll_supcon_backward", "gll_supcon_launches",
     "gll_query_workspace_bytes", "gll_knn_query", "gll_extend", "gll_query_launches",
     "gll_extend_grad_workspace_bytes", "gll_extend_backward", "gll_extend_grad_launches",
-    "gll_forward_lists_batched", "gll_graph_lists", "gll_cg_route",
+    "gll_forward_lists_batched", "gll_graph_lists", "gll_cg_route", "gll_knn_rerank",
 )
 
 
@@ -218,6 +221,9 @@ def _declare(lib):
     lib.gll_knn_query.restype = i32
     lib.gll_extend.argtypes = [i64, i64, ct.c_int32, ct.c_int32, vp, vp, vp, vp, f32, vp, vp, vp, vp]
     lib.gll_extend.restype = i32
+    lib.gll_knn_rerank.argtypes = [i64, i64, ct.c_int32, ct.c_int32, ct.c_int32, i32, vp, vp, vp, vp,
+                                   vp, vp, vp]
+    lib.gll_knn_rerank.restype = i32
     lib.gll_query_launches.argtypes = []
     lib.gll_query_launches.restype = ct.c_int64
     i32s = ct.c_int32

@@ -25,7 +25,7 @@ OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libgll.so")
 ARCH = os.environ.get("GLL_OFFLOAD_ARCH", "gfx950")
 UNITS = ["gram.hip", "select.hip", "order.hip", "ingest.hip", "rows.hip", "solve.hip", "fused_bwd.hip", "gridcg.hip", "grad.hip", "param_grad.hip", "loss.hip",
-         "features.hip", "supcon.hip", "query.hip", "extend_grad.hip", "api.hip"]
+         "features.hip", "supcon.hip", "query.hip", "rerank.hip", "extend_grad.hip", "api.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", INCLUDE, "-I", CSRC,
          "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
 

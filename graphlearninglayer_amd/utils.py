@@ -108,15 +108,19 @@ def laplace_fit(X, train_labels, knn_num=50, epsilon="auto", n_classes="auto", t
         return LaplaceFit(GLL._features(Xt, dev), P, eps, epsilon)
 
 
-def laplace_predict(fit, Xq, knn_num=50, epsilon=None):
+def laplace_predict(fit, Xq, knn_num=50, epsilon=None, neighbors=None):
     """(Uq float64 Q x C, labels int64 Q) for new points from a laplace_fit, by the harmonic
     extension over their knn_num - 1 nearest fitted points (GLL.extend): no new graph, no solve.
     epsilon: the fit's by default.  Differentiable as GLL.extend is: Uq carries a grad_fn when Xq
     (a tensor) requires grad, or fit.X / fit.P if the caller made them require grad; the fit's
-    eps gets no gradient."""
+    eps gets no gradient.
+    neighbors: Q x (knn_num - 1) lists, or a wider pool (up to 512 columns) re-ranked every call,
+    instead of the exact search (GLL.extend) -- e.g. GLL.knn_query(clean, fit.X, 4 * (knn_num - 1))
+    once, then every step of a loop that moves the queries a little."""
     Xt = Xq if torch.is_tensor(Xq) else torch.from_numpy(np.ascontiguousarray(Xq))
     return GLL.extend(Xt, fit.X, fit.P, k=knn_num,
-                      epsilon=fit.epsilon if epsilon is None else epsilon, eps_db=fit.eps)
+                      epsilon=fit.epsilon if epsilon is None else epsilon, eps_db=fit.eps,
+                      neighbors=neighbors)
 
 
 def gl_accuracy_inductive(train_data, train_label, test_data, test_label, unlabeled_data=None,

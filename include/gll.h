@@ -611,7 +611,41 @@ int gll_extend(int64_t Q, int64_t N, int32_t kn, int32_t C,
                const int32_t* idx, const float* d2 /*Q x kn*/,
                const float* P /*N x C*/, const float* eps_db /*N, or NULL*/, float eps /*>0, or <=0: auto*/,
                double* Uq /*Q x C*/, int64_t* label /*Q*/, int32_t* status, void* stream);
-int64_t gll_query_launches(void);  /* kernel launches of either call so far in this process (host counter) */
+int64_t gll_query_launches(void);  /* kernel launches of either call (and of gll_knn_rerank) so far in this process (host counter) */
+
+/* gll_knn_query's lists from caller-supplied candidates (rerank.hip): idx / d2 as
+ * gll_extend and gll_extend_backward take them, without the search.  cand: Q x c int32, for every
+ * query row c database rows -- an earlier search's lists, a wider pool searched once while the
+ * queries move, an approximate index's answer.  Distances follow gll_knn_query's contract: the value
+ * returned is the fp32 difference form (feature f on lane (f / 4) % 8 of an 8-lane group, one fmaf
+ * chain a lane in ascending f, then the 3-level tree), the value ranked the float64 fma chain over
+ * the same loads, NaN as +inf -- a pair (q, j) gets the bits gll_knn_query returns for it, from 16-B
+ * or scalar loads alike.
+ *   flags 0 (pool mode, k <= c): an entry is valid when it lies in [0, N) and no earlier entry of
+ *     its row holds the same index.  idx / d2 (Q x k): the k valid candidates nearest by (float64
+ *     d^2, index), in (returned fp32 d^2, index) order, NaN as +inf: gll_knn_query's list whenever
+ *     the pool holds the k nearest.  An invalid entry is never chosen; a row with fewer than k
+ *     valid candidates ends in (-1, +inf) entries and is counted in status[3] -- gll_extend gives
+ *     such a row NaN and counts it in status[2].
+ *   GLL_RR_KEEP_ORDER (list mode, c == k, else GLL_ERR_INVALID_ARG): idx = cand, entry by entry in
+ *     the caller's order; nothing is dropped and a repeat counts twice.  An index outside [0, N) is
+ *     kept, is not followed and gets d2 = +inf (gll_extend: a NaN weight).  The last column is what
+ *     'auto' takes eps_q from, as the layer takes eps_i from knn_ind[:, -1].
+ * status (4 device words, accumulate; the caller zeroes them): [1] rows with a non-finite returned
+ * distance among the kept (list mode: the +inf of an index out of range included); [3] pool-mode
+ * rows with fewer than k valid candidates; [0], [2] untouched.  One ordinary launch, one wave per
+ * row, four rows per 256-thread workgroup, no workspace, no atomics but atomicAdd on the status
+ * words; counted by gll_query_launches.  A row's result depends on that row, its candidates and Xdb
+ * only -- not on the rows that share the call, not on the alignment -- and two runs are bitwise
+ * equal.  Xq, Xdb need 4-B alignment only.  Q, N, d, k >= 1, k <= c (GLL_ERR_INVALID_ARG); c <= 512,
+ * k <= 256, d <= 4096, N, Q <= INT32_MAX / 2 (GLL_ERR_UNSUPPORTED); k may exceed N (the rows are
+ * short).  Stream-ordered, no allocation, no host synchronisation; argument checks come before any
+ * HIP call. */
+#define GLL_RR_KEEP_ORDER 1
+int gll_knn_rerank(int64_t Q, int64_t N, int32_t d, int32_t c, int32_t k, int flags,
+                   const float* Xq, const float* Xdb, const int32_t* cand /* Q x c */,
+                   int32_t* idx /* Q x k */, float* d2 /* Q x k */,
+                   int32_t* status /* 4 words, accumulate */, void* stream);
 
 /* Backward of gll_extend (extend_grad.hip).  The neighbour lists are frozen, as
  * the layer's kNN graph is.  For query q and list entry i, with j = idx[q, i], d_i =
