@@ -19,6 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import gll_oracle as O
+from tests import abi as A
 from tests import ce_head_ref as R
 from tests.golden_io import Case
 
@@ -34,18 +35,7 @@ def _gll():
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from graphlearninglayer_amd import _lib
-    _lib.lib()  # fail loudly when the HIP library is missing
-
-
-def _cuda(a):
-    return torch.from_numpy(np.array(a)).cuda()   # a copy: the shared inputs are read-only
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
+    A.need_gpu()
 
 
 def _layer(python=False):
@@ -79,7 +69,7 @@ def test_same_U_parity_with_pytorch(tag, eps, tau, python):
     X, Y, t = R.inputs(tag)
     k = R.CASES[tag].k
     ce, apply = _layer(python)
-    Xt, Yt, tt = _cuda(X), _cuda(Y), _cuda(t)
+    Xt, Yt, tt = A.dev(X), A.dev(Y), A.dev(t)
     loss, pred, labels, row_loss, correct = ce(Xt, Yt, tt, tau, eps, k)
     U = apply(Xt, Yt, tau, eps, k)
     m = len(t)
@@ -88,10 +78,10 @@ def test_same_U_parity_with_pytorch(tag, eps, tau, python):
     assert row_loss.shape == (m,) and row_loss.dtype == torch.float64
     assert correct.shape == () and correct.dtype == torch.int64
     assert not pred.requires_grad and loss.grad_fn is None
-    np.testing.assert_array_equal(_np(pred), _np(U))
+    np.testing.assert_array_equal(A.host(pred), A.host(U))
     tl, tr, ta = _torch_head(U, tt)
-    tl, tr, ta = float(tl), _np(tr), _np(ta)
-    a_row, a_loss = _np(row_loss), float(loss)
+    tl, tr, ta = float(tl), A.host(tr), A.host(ta)
+    a_row, a_loss = A.host(row_loss), float(loss)
     row_bound = 8 * U53 * np.maximum(np.abs(tr), 1.0)
     fin = np.isfinite(tr)
     loss_bound = (4 * m + 8) * U53 * float(np.mean(np.abs(tr[fin]))) if fin.any() else 0.0
@@ -100,11 +90,11 @@ def test_same_U_parity_with_pytorch(tag, eps, tau, python):
           f"min p_t {float(np.exp(-np.nanmax(tr))):.3g}; correct {int(correct)} / {m}")
     assert _close(a_row, tr, row_bound)
     assert _close(a_loss, tl, loss_bound)
-    Us = np.sort(_np(U), axis=1)
+    Us = np.sort(A.host(U), axis=1)
     tie = Us[:, -1] == Us[:, -2]
     assert tie.sum() <= 0.01 * m
-    np.testing.assert_array_equal(_np(labels)[~tie], ta[~tie])
-    assert int(correct) == int((_np(labels) == t).sum())
+    np.testing.assert_array_equal(A.host(labels)[~tie], ta[~tie])
+    assert int(correct) == int((A.host(labels) == t).sum())
 
 
 # ------------------------------------------------------------------------------------------
@@ -113,19 +103,15 @@ def test_same_U_parity_with_pytorch(tag, eps, tau, python):
 def _abi_head(tag, eps, tau, targets=None, want_gbar=True):
     """gll_forward + gll_ce_head_batched over ctypes; every output as numpy."""
     from graphlearninglayer_amd import _lib
-    GLL = _gll()
     X, Y, t = R.inputs(tag)
     t = t if targets is None else targets
     c = R.CASES[tag]
-    n, m = c.base + c.batch, c.batch
+    m = c.batch
     lib = _lib.lib()
-    prob = GLL.make_problem(n, c.d, c.base, c.C, c.k, tau, eps)
-    ws = torch.empty(lib.gll_workspace_bytes(ct.byref(prob)), dtype=torch.uint8, device="cuda")
-    Xt, Yt, tt = _cuda(X), _cuda(Y), _cuda(np.asarray(t, dtype=np.int64))
-    U = torch.empty(m, c.C, dtype=torch.float64, device="cuda")
-    s = torch.cuda.current_stream().cuda_stream
-    _lib.check(lib.gll_forward(ct.byref(prob), Xt.data_ptr(), Yt.data_ptr(), _lib.GLL_DT_F32,
-                               ws.data_ptr(), U.data_ptr(), s), "gll_forward")
+    run = A.Run(X, Y, c.k, tau, eps)
+    prob, ws, s = run.problem(), run.ws, A.stream()
+    tt = A.dev(np.asarray(t, dtype=np.int64))
+    U = run.forward()
     loss = torch.empty(1, dtype=torch.float64, device="cuda")
     gbar = torch.full((m, c.C), 7.0, dtype=torch.float32, device="cuda") if want_gbar else None
     row = torch.empty(m, dtype=torch.float64, device="cuda")
@@ -138,8 +124,8 @@ def _abi_head(tag, eps, tau, targets=None, want_gbar=True):
                                        row.data_ptr(), lab.data_ptr(), cor.data_ptr(),
                                        scratch.data_ptr() if sb else None, s), "gll_ce_head")
     torch.cuda.synchronize()
-    return dict(U=_np(U), loss=float(loss), gbar=_np(gbar) if want_gbar else None, row=_np(row),
-                labels=_np(lab), correct=int(cor))
+    return dict(U=U, loss=float(loss), gbar=A.host(gbar) if want_gbar else None, row=A.host(row),
+                labels=A.host(lab), correct=int(cor))
 
 
 @pytest.mark.parametrize("tag,eps,tau", [("T1", 1.0, 0.07), ("T5", 1.0, 0.07),
@@ -175,9 +161,9 @@ def _grads(tag, eps, tau, fused, need=(True, False, False, False), python=False)
     X, Y, t = R.inputs(tag)
     k = R.CASES[tag].k
     ce, apply = _layer(python)
-    Xt = _cuda(X).requires_grad_(need[0])
-    Yt = _cuda(Y).requires_grad_(need[1])
-    tt, et, tg = _scalar(tau, need[2]), _scalar(eps, need[3]), _cuda(t)
+    Xt = A.dev(X).requires_grad_(need[0])
+    Yt = A.dev(Y).requires_grad_(need[1])
+    tt, et, tg = _scalar(tau, need[2]), _scalar(eps, need[3]), A.dev(t)
     if fused:
         loss = ce(Xt, Yt, tg, tt, et, k)[0]
     else:
@@ -186,7 +172,7 @@ def _grads(tag, eps, tau, fused, need=(True, False, False, False), python=False)
     torch.cuda.synchronize()
 
     def g(v):
-        return None if not torch.is_tensor(v) or v.grad is None else _np(v.grad)
+        return None if not torch.is_tensor(v) or v.grad is None else A.host(v.grad)
     return dict(loss=float(loss.detach()), X=g(Xt), Y=g(Yt), tau=g(tt), eps=g(et))
 
 
@@ -223,7 +209,7 @@ def test_parameter_gradients_match_the_unfused_route():
 # 4. loss against the float64 oracle
 # ------------------------------------------------------------------------------------------
 def _oracle_loss_check(tagline, X, Y, t, tau, eps, k):
-    Xt, Yt, tt = _cuda(X), _cuda(Y), _cuda(t)
+    Xt, Yt, tt = A.dev(X), A.dev(Y), A.dev(t)
     loss = float(_gll().LaplaceLearningSparseHard.ce_loss(Xt, Yt, tt, tau, eps, k)[0])
     ind = _gll().device_graph(Xt, k, eps)["knn_idx"].cpu().numpy().astype(np.int64)
     Uo, _ = O.forward(X, Y, tau, eps, k, knn=(ind, None))
@@ -255,38 +241,38 @@ def test_batched_graphs_equal_single_calls():
     Ys = np.stack([R.inputs(g)[1] for g in tags])
     ts = np.stack([np.roll(R.inputs(g)[2], q) for q, g in enumerate(tags)])   # per-graph targets
     L = _gll().LaplaceLearningSparseHard
-    Xb = _cuda(Xs).requires_grad_(True)
-    lossb, predb, labb, rowb, corb = L.ce_loss(Xb, _cuda(Ys), _cuda(ts), tau, eps, k)
+    Xb = A.dev(Xs).requires_grad_(True)
+    lossb, predb, labb, rowb, corb = L.ce_loss(Xb, A.dev(Ys), A.dev(ts), tau, eps, k)
     assert lossb.shape == (3,) and corb.shape == (3,) and rowb.shape == ts.shape
     assert labb.shape == ts.shape and predb.shape == (3, ts.shape[1], Ys.shape[2])
     lossb.sum().backward()
-    gb = _np(Xb.grad)
+    gb = A.host(Xb.grad)
     # apply's own batched backward on the same loss: bitwise the single call or not?
-    Xa = _cuda(Xs).requires_grad_(True)
-    Ua = L.apply(Xa, _cuda(Ys), tau, eps, k)
-    sum(_gll().custom_ce_loss(Ua[g], _cuda(ts[g])) for g in range(3)).backward()
+    Xa = A.dev(Xs).requires_grad_(True)
+    Ua = L.apply(Xa, A.dev(Ys), tau, eps, k)
+    sum(_gll().custom_ce_loss(Ua[g], A.dev(ts[g])) for g in range(3)).backward()
     for g in range(3):
-        X1 = _cuda(Xs[g]).requires_grad_(True)
-        loss, pred, lab, row, cor = L.ce_loss(X1, _cuda(Ys[g]), _cuda(ts[g]), tau, eps, k)
+        X1 = A.dev(Xs[g]).requires_grad_(True)
+        loss, pred, lab, row, cor = L.ce_loss(X1, A.dev(Ys[g]), A.dev(ts[g]), tau, eps, k)
         loss.backward()
         assert float(loss.detach()) == float(lossb[g].detach()) and int(cor) == int(corb[g])
-        np.testing.assert_array_equal(_np(row), _np(rowb[g]))
-        np.testing.assert_array_equal(_np(lab), _np(labb[g]))
-        np.testing.assert_array_equal(_np(pred), _np(predb[g]))
-        Xs1 = _cuda(Xs[g]).requires_grad_(True)
-        _gll().custom_ce_loss(L.apply(Xs1, _cuda(Ys[g]), tau, eps, k), _cuda(ts[g])).backward()
-        apply_bitwise = np.array_equal(_np(Xa.grad[g]), _np(Xs1.grad))
-        e = O.rel_err(gb[g], _np(X1.grad))
+        np.testing.assert_array_equal(A.host(row), A.host(rowb[g]))
+        np.testing.assert_array_equal(A.host(lab), A.host(labb[g]))
+        np.testing.assert_array_equal(A.host(pred), A.host(predb[g]))
+        Xs1 = A.dev(Xs[g]).requires_grad_(True)
+        _gll().custom_ce_loss(L.apply(Xs1, A.dev(Ys[g]), tau, eps, k), A.dev(ts[g])).backward()
+        apply_bitwise = np.array_equal(A.host(Xa.grad[g]), A.host(Xs1.grad))
+        e = O.rel_err(gb[g], A.host(X1.grad))
         print(f"graph {g}: apply batched == single bitwise: {apply_bitwise}; "
               f"ce_loss batched vs single grad_X rel err {e:.2e}")
         if apply_bitwise:
-            np.testing.assert_array_equal(gb[g], _np(X1.grad))
+            np.testing.assert_array_equal(gb[g], A.host(X1.grad))
         else:   # other kernel variants in the batched launch: test_gpu_parity's bar for them
             assert e <= 1e-5
     # one graph's loss alone: the others get an exact-zero gradient
-    Xc = _cuda(Xs).requires_grad_(True)
-    L.ce_loss(Xc, _cuda(Ys), _cuda(ts), tau, eps, k)[0][1].backward()
-    gc = _np(Xc.grad)
+    Xc = A.dev(Xs).requires_grad_(True)
+    L.ce_loss(Xc, A.dev(Ys), A.dev(ts), tau, eps, k)[0][1].backward()
+    gc = A.host(Xc.grad)
     assert (gc[0] == 0).all() and (gc[2] == 0).all()
     np.testing.assert_array_equal(gc[1], gb[1])
 
@@ -319,14 +305,14 @@ def test_masked_targets():
     assert rel.max() <= 2.0 ** -23 and (out["gbar"][~hot] == 0).all()
     # the same through autograd: masked rows pull no gradient, the others keep the divisor m
     L = _gll().LaplaceLearningSparseHard
-    Xt = _cuda(X).requires_grad_(True)
-    loss, _, _, row, cor = L.ce_loss(Xt, _cuda(Y), _cuda(tm), 0.07, 1.0, R.CASES["T1"].k)
+    Xt = A.dev(X).requires_grad_(True)
+    loss, _, _, row, cor = L.ce_loss(Xt, A.dev(Y), A.dev(tm), 0.07, 1.0, R.CASES["T1"].k)
     loss.backward()
     assert float(loss) == out["loss"] and int(cor) == out["correct"]
-    Xr = _cuda(X).requires_grad_(True)
-    U = L.apply(Xr, _cuda(Y), 0.07, 1.0, R.CASES["T1"].k)
-    U.backward(_cuda(ref.gbar))
-    e = O.rel_err(_np(Xt.grad), _np(Xr.grad))
+    Xr = A.dev(X).requires_grad_(True)
+    U = L.apply(Xr, A.dev(Y), 0.07, 1.0, R.CASES["T1"].k)
+    U.backward(A.dev(ref.gbar))
+    e = O.rel_err(A.host(Xt.grad), A.host(Xr.grad))
     print(f"masked: grad_X rel err against apply fed the reference gbar {e:.2e}")
     assert e < TOL
 
@@ -342,38 +328,31 @@ def test_launch_accounting():
     def counts(fused, tag, eps, tau):
         out = {}
         for kid in kids:   # one kernel id at a time: a bracket pair is armed per thread
-            _lib.prof_enable(kid, 1)
-            _grads(tag, eps, tau, fused)
-            out[kid] = _lib.prof_read(kid)[1]
-            _lib.prof_enable(kid, 0)
+            with A.launches(kid) as ran:
+                _grads(tag, eps, tau, fused)
+            out[kid] = ran[0]
         return out
 
-    try:
-        # T1 / T2: adjoint CG + gradient launches (fixed / auto eps); NS: the fused backward
-        for tag, eps, tau in (("T1", 1.0, 0.07), ("T2", "auto", 0.0), R.NS):
-            _grads(tag, eps, tau, True)   # warm
-            a, b = counts(True, tag, eps, tau), counts(False, tag, eps, tau)
-            print(f"{tag}: launches ce_loss {a}, apply {b}")
-            assert a[_lib.K_LOSS] == 1 and b[_lib.K_LOSS] == 0
-            for kid in kids[:-1]:
-                assert a[kid] == b[kid], _lib.kernel_name(kid)
-            assert sum(a[kid] for kid in kids[:-1]) >= 5
-            if tag == "NS":
-                assert a[_lib.K_BWD] == 1   # the saved gbar still takes the one-launch backward
-        # m = 2048 still takes one launch and no scratch
-        from graphlearninglayer_amd.synth import one_hot, synth
-        X, lab = synth(16, 2048, 16, C=3, r=0.75, seed=0)
-        _lib.prof_enable(_lib.K_LOSS, 1)
-        with torch.no_grad():
-            _gll().LaplaceLearningSparseHard.ce_loss(_cuda(X), _cuda(one_hot(lab[:16], 3)),
-                                                     _cuda(lab[16:]), 0.07, 1.0, 6)
-        assert _lib.prof_read(_lib.K_LOSS)[1] == 1
-        p = _gll().make_problem(2064, 16, 16, 3, 6, 0.07, 1.0)
-        assert _lib.lib().gll_ce_head_scratch_bytes(ct.byref(p), 1) == 0
-    finally:
-        for kid in kids:
-            _lib.prof_enable(kid, 0)
-            _lib.prof_read(kid)
+    # T1 / T2: adjoint CG + gradient launches (fixed / auto eps); NS: the fused backward
+    for tag, eps, tau in (("T1", 1.0, 0.07), ("T2", "auto", 0.0), R.NS):
+        _grads(tag, eps, tau, True)   # warm
+        a, b = counts(True, tag, eps, tau), counts(False, tag, eps, tau)
+        print(f"{tag}: launches ce_loss {a}, apply {b}")
+        assert a[_lib.K_LOSS] == 1 and b[_lib.K_LOSS] == 0
+        for kid in kids[:-1]:
+            assert a[kid] == b[kid], _lib.kernel_name(kid)
+        assert sum(a[kid] for kid in kids[:-1]) >= 5
+        if tag == "NS":
+            assert a[_lib.K_BWD] == 1   # the saved gbar still takes the one-launch backward
+    # m = 2048 still takes one launch and no scratch
+    from graphlearninglayer_amd.synth import one_hot, synth
+    X, lab = synth(16, 2048, 16, C=3, r=0.75, seed=0)
+    with A.launches(_lib.K_LOSS) as ran, torch.no_grad():
+        _gll().LaplaceLearningSparseHard.ce_loss(A.dev(X), A.dev(one_hot(lab[:16], 3)),
+                                                 A.dev(lab[16:]), 0.07, 1.0, 6)
+    assert ran == [1]
+    p = _gll().make_problem(2064, 16, 16, 3, 6, 0.07, 1.0)
+    assert _lib.lib().gll_ce_head_scratch_bytes(ct.byref(p), 1) == 0
 
 
 # ------------------------------------------------------------------------------------------
@@ -384,25 +363,25 @@ def test_no_grad_and_consumed_graph(python):
     X, Y, t = R.inputs("T1")
     k = R.CASES["T1"].k
     ce, _ = _layer(python)
-    Xt = _cuda(X).requires_grad_(True)
-    full = ce(Xt, _cuda(Y), _cuda(t), 0.07, 1.0, k)
+    Xt = A.dev(X).requires_grad_(True)
+    full = ce(Xt, A.dev(Y), A.dev(t), 0.07, 1.0, k)
     assert full[0].requires_grad and not any(o.requires_grad for o in full[1:])
     with torch.no_grad():
-        ng = ce(Xt, _cuda(Y), _cuda(t), 0.07, 1.0, k)
-    plain = ce(_cuda(X), _cuda(Y), _cuda(t), 0.07, 1.0, k)   # no input requires grad
+        ng = ce(Xt, A.dev(Y), A.dev(t), 0.07, 1.0, k)
+    plain = ce(A.dev(X), A.dev(Y), A.dev(t), 0.07, 1.0, k)   # no input requires grad
     for outs in (ng, plain):
         assert not outs[0].requires_grad and outs[0].grad_fn is None
         for a, b in zip(outs, full):
-            np.testing.assert_array_equal(_np(a), _np(b))
+            np.testing.assert_array_equal(A.host(a), A.host(b))
     full[0].backward()
     with pytest.raises(RuntimeError):
         full[0].backward()
     # argument handling: shapes and dtypes of targets
     with pytest.raises(ValueError):
-        ce(_cuda(X), _cuda(Y), _cuda(t[:-1]), 0.07, 1.0, k)
+        ce(A.dev(X), A.dev(Y), A.dev(t[:-1]), 0.07, 1.0, k)
     with pytest.raises(TypeError):
-        ce(_cuda(X), _cuda(Y), _cuda(t.astype(np.float32)), 0.07, 1.0, k)
-    i32 = ce(_cuda(X), _cuda(Y), _cuda(t.astype(np.int32)), 0.07, 1.0, k)
+        ce(A.dev(X), A.dev(Y), A.dev(t.astype(np.float32)), 0.07, 1.0, k)
+    i32 = ce(A.dev(X), A.dev(Y), A.dev(t.astype(np.int32)), 0.07, 1.0, k)
     assert float(i32[0]) == float(full[0])
     # CPU input: every output comes back on the CPU, the gradient too
     Xc = torch.from_numpy(np.array(X)).requires_grad_(True)
@@ -410,7 +389,7 @@ def test_no_grad_and_consumed_graph(python):
     assert all(o.device.type == "cpu" for o in outs)
     outs[0].backward()
     assert Xc.grad.device.type == "cpu" and float(outs[0]) == float(full[0])
-    np.testing.assert_array_equal(Xc.grad.numpy(), _np(Xt.grad))
+    np.testing.assert_array_equal(Xc.grad.numpy(), A.host(Xt.grad))
 
 
 # ------------------------------------------------------------------------------------------
@@ -425,7 +404,7 @@ def test_three_step_sgd_loop():
         torch.manual_seed(0)
         net = torch.nn.Linear(16, 16).cuda()
         opt = torch.optim.SGD(net.parameters(), lr=0.1)
-        Xt, Yt, tt = _cuda(X), _cuda(Y), _cuda(t)
+        Xt, Yt, tt = A.dev(X), A.dev(Y), A.dev(t)
         losses = []
         for _ in range(3):
             opt.zero_grad()
@@ -437,7 +416,7 @@ def test_three_step_sgd_loop():
             loss.backward()
             opt.step()
             losses.append(float(loss))
-        return np.concatenate([_np(p).ravel() for p in net.parameters()]), losses
+        return np.concatenate([A.host(p).ravel() for p in net.parameters()]), losses
 
     pa, la = train(True)
     pb, lb = train(False)

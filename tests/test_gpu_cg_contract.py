@@ -62,165 +62,84 @@ iteration counts: the recursive residual it stops on had drifted from the true o
 solves now run the kernel's Chronopoulos-Gear form, as gll_cg_csr did already (rho 1.25e-6 and
 1.15e-6 on the same two cases).
 """
-import ctypes as ct
-
 import numpy as np
 import pytest
 import torch
 
+from graphlearninglayer_amd import GLL
+from graphlearninglayer_amd import _lib as L
 from oracle import gll_oracle as O
+from tests import abi as A
 from tests import cg_ref as R
 
 pytestmark = pytest.mark.gpu
-ITERATE_TOL = 1e-5     # between two CG kernels (tests/test_gpu_parity.py)
+ITERATE_TOL = 1e-5     # between two CG kernels (tests/test_gpu_cg.py)
 GBAR_ZERO_COL = 3
-
-
-def _lib():
-    from graphlearninglayer_amd import _lib
-    return _lib
-
-
-def _gll():
-    from graphlearninglayer_amd import GLL
-    return GLL
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    _lib().lib()  # fail loudly when the HIP library is missing
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+    A.need_gpu()
 
 
 class Session:
-    """One case on the device: features of its B graphs, B workspace blocks, optional sink."""
+    """One case on the device (tests/abi.py Run): its B graphs and workspace blocks, optional
+    sink; every call under the case's GLL_KNOB_VR_RV (the workspace layout reads it) with the CG
+    and fused-backward launches bracketed."""
 
     def __init__(self, case, sink=False):
-        L = _lib()
         self.case, self.B = case, case.B
         xy = [R.features(case, g) for g in range(case.B)]
+        Xh = np.stack([x for x, _ in xy])
         self.Yh = np.stack([y for _, y in xy])
-        self.X = torch.from_numpy(np.stack([x for x, _ in xy])).cuda()
-        self.Y = torch.from_numpy(self.Yh).cuda()
-        self.sink = torch.zeros(L.ST_NWORDS, dtype=torch.int32, device="cuda") if sink else None
-        self.wb = self._knobbed(lambda: L.lib().gll_workspace_bytes(ct.byref(self.problem())))
-        assert self.wb > 0
-        self.ws = torch.empty(self.B * self.wb, dtype=torch.uint8, device="cuda")
-        self.U = torch.empty(self.B, case.m, case.C, dtype=torch.float64, device="cuda")
-        self.gx = torch.empty(self.B, case.n, R.D_FEAT, dtype=torch.float32, device="cuda")
+        one = case.B == 1
+        with self._knobbed():
+            self.run = A.Run(Xh[0] if one else Xh, self.Yh[0] if one else self.Yh, case.k, case.tau,
+                             case.eps, case.flags, rtol=1e-6, max_iter=1000, sink=sink)
+        self.sink = self.run.sink
 
-    def problem(self, rtol=1e-6, max_iter=1000, flags=None):
+    def _knobbed(self):
+        return A.knobs({L.KNOB_VR_RV: self.case.knob_rv})
+
+    def _status(self):
+        return [self.run.status(g) for g in range(self.B)]
+
+    def _solutions(self, field):
+        """The m x C fp32 array `field` of every graph's view."""
         c = self.case
-        p = _gll().make_problem(c.n, R.D_FEAT, c.base, c.C, c.k, c.tau, c.eps, rtol=rtol,
-                                max_iter=max_iter, flags=c.flags if flags is None else flags)
-        if self.sink is not None:
-            p.status_sink = self.sink.data_ptr()
-        return p
-
-    def _knobbed(self, call):
-        """`call` with the case's GLL_KNOB_VR_RV (the workspace layout reads it), restored after."""
-        L = _lib()
-        L.set_knob(L.KNOB_VR_RV, self.case.knob_rv)
-        try:
-            return call()
-        finally:
-            L.set_knob(L.KNOB_VR_RV, 0)
-
-    def _bracketed(self, call):
-        """Run `call` with the case's knob set and every CG / fused-backward launch bracketed:
-        (K_CG launches, K_BWD launches)."""
-        L = _lib()
-        L.set_knob(L.KNOB_VR_RV, self.case.knob_rv)
-        L.prof_enable(L.K_CG, 1)
-        L.prof_enable(L.K_BWD, 1)
-        try:
-            call()
-            torch.cuda.synchronize()
-            return L.prof_read(L.K_CG)[1], L.prof_read(L.K_BWD)[1]
-        finally:
-            L.prof_enable(L.K_CG, 0)
-            L.prof_enable(L.K_BWD, 0)
-            L.set_knob(L.KNOB_VR_RV, 0)
-
-    def status(self, g=0):
-        return self.ws[g * self.wb: g * self.wb + 4 * _lib().ST_NWORDS].view(torch.int32).cpu().tolist()
-
-    def _arr(self, ptr, count, dtype):
-        off = ptr - self.ws.data_ptr()
-        return self.ws[off: off + 4 * count].view(dtype)
-
-    def view(self, g=0):
-        L = _lib()
-        v = L.View()
-        p = self.problem()
-        L.check(self._knobbed(lambda: L.lib().gll_workspace_view(
-            ct.byref(p), self.ws.data_ptr() + g * self.wb, ct.byref(v))), "gll_workspace_view")
-        return v
+        with self._knobbed():
+            return np.stack([self.run.array(getattr(self.run.view(g), field), c.m * c.C, np.float32,
+                                            g).reshape(c.m, c.C) for g in range(self.B)])
 
     def forward(self, rtol=1e-6, max_iter=1000):
         """(U B x m x C float64, U32, status words per graph or of the sink, CG launches)."""
-        L = _lib()
-        lib = L.lib()
-        p = self.problem(rtol, max_iter)
-
-        def call():
-            if self.B == 1:
-                rc = lib.gll_forward(ct.byref(p), self.X.data_ptr(), self.Y.data_ptr(), L.GLL_DT_F32,
-                                     self.ws.data_ptr(), self.U.data_ptr(), _stream())
-            else:
-                rc = lib.gll_forward_batched(ct.byref(p), self.B, self.X.data_ptr(),
-                                             self.Y.data_ptr(), L.GLL_DT_F32, self.ws.data_ptr(),
-                                             self.U.data_ptr(), _stream())
-            L.check(rc, "gll_forward")
-        ncg, _ = self._bracketed(call)
         c = self.case
-        U32 = np.stack([self._arr(self.view(g).U32, c.m * c.C, torch.float32)
-                        .reshape(c.m, c.C).cpu().numpy() for g in range(self.B)])
-        return self.U.cpu().numpy(), U32, [self.status(g) for g in range(self.B)], ncg
+        with self._knobbed(), A.launches(L.K_CG, L.K_BWD) as ran:
+            U = self.run.forward(rtol=rtol, max_iter=max_iter)
+        return U.reshape(self.B, c.m, c.C), self._solutions("U32"), self._status(), ran[0]
 
     def backward(self, gbar, g_dtype, rtol=1e-6, max_iter=1000):
         """(grad_X, wadj B x m x C fp32, status per graph, (CG launches, fused launches))."""
-        L = _lib()
-        lib = L.lib()
-        p = self.problem(rtol, max_iter)
-        gd = torch.from_numpy(np.ascontiguousarray(
-            gbar, dtype=np.float32 if g_dtype == L.GLL_DT_F32 else np.float64)).cuda()
-
-        def call():
-            if self.B == 1:
-                rc = lib.gll_backward(ct.byref(p), self.X.data_ptr(), self.Y.data_ptr(),
-                                      L.GLL_DT_F32, self.ws.data_ptr(), gd.data_ptr(), g_dtype,
-                                      self.gx.data_ptr(), _stream())
-            else:
-                rc = lib.gll_backward_batched(ct.byref(p), self.B, self.X.data_ptr(),
-                                              self.ws.data_ptr(), gd.data_ptr(), g_dtype,
-                                              self.gx.data_ptr(), _stream())
-            L.check(rc, "gll_backward")
-        launches = self._bracketed(call)
         c = self.case
-        wadj = np.stack([self._arr(self.view(g).wadj, c.m * c.C, torch.float32)
-                         .reshape(c.m, c.C).cpu().numpy() for g in range(self.B)])
-        return self.gx.cpu().numpy(), wadj, [self.status(g) for g in range(self.B)], launches
+        with self._knobbed(), A.launches(L.K_CG, L.K_BWD) as ran:
+            gx = self.run.backward(gbar, g_dtype, rtol=rtol, max_iter=max_iter)
+        return gx.reshape(self.B, c.n, R.D_FEAT), self._solutions("wadj"), self._status(), tuple(ran)
 
     def systems(self):
         """[(Luu, W_ul @ Y)] per graph from the workspace arrays a forward left."""
-        c = self.case
+        c, run = self.case, self.run
         out = []
         for g in range(self.B):
-            v = self.view(g)
-            rs = self._arr(v.row_start, c.n, torch.int32).cpu().numpy()
-            rl = self._arr(v.row_len, c.n, torch.int32).cpu().numpy()
+            with self._knobbed():
+                v = run.view(g)
+            rs = run.array(v.row_start, c.n, np.int32, g)
+            rl = run.array(v.row_len, c.n, np.int32, g)
             E = int((rs.astype(np.int64) + rl).max())
-            col = self._arr(v.col, E, torch.int32).cpu().numpy()
-            w = self._arr(v.w, E, torch.float32).cpu().numpy()
-            deg = self._arr(v.deg, c.n, torch.float32).cpu().numpy()
-            A, Wul = R.luu_from_view(rs, rl, col, w, deg, c.tau, c.base)
-            out.append((A, np.asarray(Wul @ self.Yh[g].astype(np.float64))))
+            col = run.array(v.col, E, np.int32, g)
+            w = run.array(v.w, E, np.float32, g)
+            deg = run.array(v.deg, c.n, np.float32, g)
+            Luu, Wul = R.luu_from_view(rs, rl, col, w, deg, c.tau, c.base)
+            out.append((Luu, np.asarray(Wul @ self.Yh[g].astype(np.float64))))
         return out
 
 
@@ -293,7 +212,6 @@ def _kernel_ran(case, st, ncg):
     route for the case's problem (gll_cg_route: what cg_dispatch launches from); exactly one CG
     launch was bracketed per forward, and the whole-GPU route was (or, injected, was not) left
     alone."""
-    L = _lib()
     assert R.route(case.n, case.base, case.C, case.k, case.flags, case.B, case.knob_rv) == \
         (case.kernel, case.precond)
     rc, name, words = R.lib_route(case.n, case.base, case.C, case.k, case.flags, case.B,
@@ -307,7 +225,6 @@ def _kernel_ran(case, st, ncg):
 
 @pytest.mark.parametrize("name", [c.name for c in ALL_FORWARD])
 def test_forward_residual_iterations_and_rtol(name):
-    L = _lib()
     case = {c.name: c for c in ALL_FORWARD}[name]
     ses = Session(case)
     runs = {rtol: ses.forward(rtol) for rtol in R.RTOLS}
@@ -328,7 +245,6 @@ def test_forward_residual_iterations_and_rtol(name):
 
 @pytest.mark.parametrize("name", [c.name for c in ALL_FORWARD])
 def test_forward_max_iter_cap(name):
-    L = _lib()
     case = {c.name: c for c in ALL_FORWARD}[name]
     ses = Session(case)
     U, U32, st, ncg = ses.forward(1e-6, max_iter=2)
@@ -347,7 +263,7 @@ def test_forward_max_iter_cap(name):
     assert max(errs) <= ITERATE_TOL
     if name == "ell_neumann_m500":
         with pytest.warns(RuntimeWarning, match="reached max_iter"):
-            _gll()._warn_from(st[0])
+            GLL._warn_from(st[0])
     # the backward after a capped forward: finite, and not reported as a failed solve
     gbar = np.stack([_gbar(case, g) for g in range(case.B)])
     gx, wadj, stb, _ = ses.backward(gbar, L.GLL_DT_F32, 1e-6, max_iter=2)
@@ -375,7 +291,6 @@ def test_batched_status_sink_holds_graph_zero_and_capped_columns_and_is_sticky()
     """gll.h: with a status_sink the *_ITERS words hold the iterations of graph 0 and of every
     column that hit max_iter; the words accumulate across calls.  Without one, each graph's own
     workspace block holds its own words (checked per graph in the tests above)."""
-    L = _lib()
     case = R.CASES["ell_jacobi_256x2_B27"]
     own = Session(case)
     _, _, st_own, _ = own.forward(1e-6)
@@ -386,7 +301,7 @@ def test_batched_status_sink_holds_graph_zero_and_capped_columns_and_is_sticky()
     _note(f"batched sink: own-block iterations {its}, sink word {sink[L.ST_FWD_ITERS]}")
     assert sink[L.ST_FWD_ITERS] == its[0] and sink[L.ST_FWD_NONCONV] == 0
     assert max(its) > its[0]      # other graphs take more (textbook: 11 against 12): not a maximum
-    assert np.array_equal(U, own.U.cpu().numpy())                   # the sink changes no result
+    assert np.array_equal(U, A.host(own.run.U))                   # the sink changes no result
     assert all(s[L.ST_FWD_ITERS] == 0 and s[L.ST_FWD_NONCONV] == 0 for s in st_ws)
     # capped: every live column of every graph reports, twice over two calls
     live = case.B * (case.C - 1)
@@ -403,7 +318,7 @@ def test_batched_status_sink_holds_graph_zero_and_capped_columns_and_is_sticky()
     assert s3[L.ST_BWD_ITERS] == 2 and s3[L.ST_BWD_NONCONV] == live
     assert s3[L.ST_FWD_NONCONV] == 2 * live
     with pytest.warns(RuntimeWarning, match="reached max_iter"):
-        _gll()._warn_from(s3)
+        GLL._warn_from(s3)
 
 
 # ------------------------------------------------------------------------------------------
@@ -423,7 +338,6 @@ def test_adjoint_residual_iterations_rtol_and_cap(name, g_dtype):
     """wadj (read from the view) of gll_backward(_batched) under the forward's four rules and the
     max_iter cap.  The right-hand side is gbar as the kernels read it: rounded to fp32."""
     import dataclasses
-    L = _lib()
     fwd_name, extra, launches, precond = ADJOINT[name]
     case = dataclasses.replace(R.CASES[fwd_name], flags=R.CASES[fwd_name].flags | extra)
     assert R.route(case.n, case.base, case.C, case.k, case.flags, case.B)[1] == precond
@@ -464,7 +378,7 @@ def test_adjoint_residual_iterations_rtol_and_cap(name, g_dtype):
     _note(f"{tag} max_iter 2: second iterate vs textbook, worst rel err {max(errs):.2e}")
     assert max(errs) <= ITERATE_TOL
     with pytest.warns(RuntimeWarning, match="adjoint CG.*reached max_iter"):
-        _gll()._warn_from(st[0])
+        GLL._warn_from(st[0])
     ses.forward()
     cap = max(int(ref.it[1e-6].max()) for ref in refs) + 1
     _, _, st, _ = ses.backward(gbar, dt, 1e-6, max_iter=cap)
@@ -477,29 +391,23 @@ def test_adjoint_residual_iterations_rtol_and_cap(name, g_dtype):
 def _cg_csr(rp, col, val, b, atol, max_iter, ws="auto", counters=True, it_nc=None):
     """gll_cg_csr: (return code, x, iters, nonconv, CG launches).  `it_nc`: device counters to
     accumulate into (default: fresh zeroed ones)."""
-    L = _lib()
     lib = L.lib()
     m, C = b.shape
     d = [torch.from_numpy(a).cuda() for a in (rp, col, val, b)]
-    x = torch.full((m, C), float("nan"), dtype=torch.float32, device="cuda")
+    x = A.nan(m, C, dtype=torch.float32)
     if it_nc is None:
         it_nc = torch.zeros(2, dtype=torch.int32, device="cuda")
     wsd = None
     if ws == "auto":
         wsd = torch.empty(max(lib.gll_cg_csr_workspace_bytes(m, C), 4), dtype=torch.uint8, device="cuda")
-    L.prof_enable(L.K_CG, 1)
-    try:
+    with A.launches(L.K_CG) as ran:
         rc = lib.gll_cg_csr(m, C, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
                             x.data_ptr(), float(atol), int(max_iter),
                             it_nc.data_ptr() if counters else None,
                             it_nc[1:].data_ptr() if counters else None,
-                            wsd.data_ptr() if wsd is not None else None, _stream())
-        torch.cuda.synchronize()
-        ncg = L.prof_read(L.K_CG)[1]
-    finally:
-        L.prof_enable(L.K_CG, 0)
+                            wsd.data_ptr() if wsd is not None else None, A.stream())
     it, nc = it_nc.cpu().tolist()
-    return rc, x.cpu().numpy(), it, nc, ncg
+    return rc, x.cpu().numpy(), it, nc, ran[0]
 
 
 @pytest.mark.parametrize("m,C,kernel", R.CSR_ROUTES)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import abi as A
 from tests import extend_grad_ref as E
 from tests import query_ref as R
 
@@ -35,9 +36,7 @@ def _G():
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    _L().lib()  # fail loudly when the HIP library is missing
+    A.need_gpu()
     yield
     try:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
@@ -45,10 +44,6 @@ def _need_gpu():
             json.dump(PARITY, fh, indent=1, sort_keys=True)
     except OSError:
         pass
-
-
-def _dev(a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()   # a copy: the cases are read-only
 
 
 def _what(epsilon):
@@ -60,8 +55,8 @@ def _what(epsilon):
 def _gpu_case(name):
     """The case on the device with the GPU's own lists: (xq, xdb, p, e32, idx int32, d2, gu, eps)."""
     Xq, Xdb, P, k, epsilon, eps_db, gU, idx_ref, d2_ref = E.grad_case(name)
-    xq, xdb, p, gu = _dev(Xq), _dev(Xdb), _dev(P), _dev(gU)
-    e32 = None if eps_db is None else _dev(eps_db)
+    xq, xdb, p, gu = A.dev(Xq), A.dev(Xdb), A.dev(P), A.dev(gU)
+    e32 = None if eps_db is None else A.dev(eps_db)
     idx, d2 = _G().knn_query(xq, xdb, k - 1)
     assert (np.sort(idx.cpu().numpy(), axis=1) == np.sort(idx_ref, axis=1)).all()
     return xq, xdb, p, e32, idx.int().contiguous(), d2, gu, 0.0 if epsilon == "auto" else float(epsilon)
@@ -76,10 +71,6 @@ def _stage(name, what, flags=0, rows=None, idx=None):
     out = _G()._extend_backward_device(xq, xdb, idx, d2, p, e32, eps, gu, what, flags)
     torch.cuda.synchronize()
     return dict(zip(KEYS + ("status",), out))
-
-
-def _bits(t):
-    return None if t is None else t.detach().cpu().numpy().tobytes()
 
 
 # ------------------------------------------------------------------------------------------
@@ -109,7 +100,7 @@ def test_stage_within_the_derived_bound_and_what_bits_agree(name):
     for bit, key in ((L.EG_XQ, "gXq"), (L.EG_XDB, "gXdb"), (L.EG_P, "gP"), (L.EG_EPS, "geps")):
         if what & bit:
             one = _stage(name, bit)
-            assert _bits(one[key]) == _bits(got[key]), key
+            assert A.raw_bytes(one[key]) == A.raw_bytes(got[key]), key
             assert all(one[o] is None for o in KEYS if o != key)
 
 
@@ -129,7 +120,7 @@ def test_misaligned_storage_gives_the_aligned_bits():
     for mq, mdb in ((shifted(xq), xdb), (xq, shifted(xdb)), (shifted(xq), shifted(xdb))):
         out = _G()._extend_backward_device(mq, mdb, idx, shifted(d2), shifted(p), e32, eps, gu, 15)
         for key, t in zip(KEYS, out):
-            assert _bits(t) == _bits(ref[key]), key
+            assert A.raw_bytes(t) == A.raw_bytes(ref[key]), key
 
 
 # ------------------------------------------------------------------------------------------
@@ -155,14 +146,14 @@ def test_end_to_end_against_float64_autograd(name):
     Xq, Xdb, P, k, epsilon, eps_db, gU, *_ = E.grad_case(name)
     ref = _torch_grads(name, torch.float64, "cpu")
     f32 = _torch_grads(name, torch.float32, "cuda")
-    xq, xdb, p = (_dev(a).requires_grad_(True) for a in (Xq, Xdb, P))
+    xq, xdb, p = (A.dev(a).requires_grad_(True) for a in (Xq, Xdb, P))
     eps = epsilon
     if epsilon != "auto":
         eps = torch.tensor(float(epsilon), dtype=torch.float64, device="cuda", requires_grad=True)
     Uq, labels = _G().extend(xq, xdb, p, k=k, epsilon=eps,
-                             eps_db=None if eps_db is None else _dev(eps_db))
+                             eps_db=None if eps_db is None else A.dev(eps_db))
     assert Uq.grad_fn is not None and Uq.dtype == torch.float64 and not labels.requires_grad
-    (Uq * _dev(gU)).sum().backward()
+    (Uq * A.dev(gU)).sum().backward()
     assert xq.grad.dtype == torch.float32 and xdb.grad.shape == xdb.shape and p.grad.shape == p.shape
     ours = [xq.grad, xdb.grad, p.grad, None if epsilon == "auto" else eps.grad.reshape(1)]
     if epsilon != "auto":
@@ -188,23 +179,23 @@ def test_end_to_end_against_float64_autograd(name):
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16, torch.float64])
 def test_gradients_come_back_in_each_inputs_dtype(dtype):
     Xq, Xdb, P, k, epsilon, eps_db, gU, *_ = E.grad_case("fixed")
-    xq = _dev(Xq).to(dtype).requires_grad_(True)
-    xdb = _dev(Xdb).to(dtype).requires_grad_(True)
-    p = _dev(P).to(dtype).requires_grad_(True)
+    xq = A.dev(Xq).to(dtype).requires_grad_(True)
+    xdb = A.dev(Xdb).to(dtype).requires_grad_(True)
+    p = A.dev(P).to(dtype).requires_grad_(True)
     Uq, _ = _G().extend(xq, xdb, p, k=k, epsilon=epsilon)
-    (Uq * _dev(gU)).sum().backward()
+    (Uq * A.dev(gU)).sum().backward()
     assert xq.grad.dtype == dtype and xdb.grad.dtype == dtype and p.grad.dtype == dtype
     # the values are those of the same call on the float32 casts torch makes
     a, b, c = (t.detach().float().requires_grad_(True) for t in (xq, xdb, p))
     U2, _ = _G().extend(a, b, c, k=k, epsilon=epsilon)
-    (U2 * _dev(gU)).sum().backward()
-    assert _bits(U2) == _bits(Uq)
+    (U2 * A.dev(gU)).sum().backward()
+    assert A.raw_bytes(U2) == A.raw_bytes(Uq)
     assert torch.equal(a.grad.to(dtype), xq.grad) and torch.equal(c.grad.to(dtype), p.grad)
     # only what requires grad is computed; eps_db never gets a gradient
-    e = _dev(E.grad_case("auto")[5]).requires_grad_(True)
+    e = A.dev(E.grad_case("auto")[5]).requires_grad_(True)
     Xa, Xda, Pa, ka, *_ = E.grad_case("auto")
-    q = _dev(Xa).requires_grad_(True)
-    U3, _ = _G().extend(q, _dev(Xda), _dev(Pa), k=ka, epsilon="auto", eps_db=e)
+    q = A.dev(Xa).requires_grad_(True)
+    U3, _ = _G().extend(q, A.dev(Xda), A.dev(Pa), k=ka, epsilon="auto", eps_db=e)
     U3.sum().backward()
     assert e.grad is None and q.grad is not None
 
@@ -219,7 +210,7 @@ def test_runs_repeat_and_small_lists_give_the_default_bits(name):
     a, b = _stage(name, what), _stage(name, what)
     s = _stage(name, what, flags=L.EGF_SMALL_LISTS)
     for key in KEYS:
-        assert _bits(a[key]) == _bits(b[key]) == _bits(s[key]), key
+        assert A.raw_bytes(a[key]) == A.raw_bytes(b[key]) == A.raw_bytes(s[key]), key
     # nine rows of the hub case list more than 64 queries, none more than 512
     assert a["status"].cpu()[L.EGST_LONG_LIST] == 0 and s["status"].cpu()[L.EGST_LONG_LIST] == 9
     lens = np.bincount(_gpu_case(name)[4].cpu().numpy().ravel(), minlength=500)
@@ -235,13 +226,13 @@ def test_row_of_a_call_equals_the_call_on_that_row(name):
     Q = full.shape[0]
     for q in sorted({0, Q // 2, Q - 1}):
         one = _stage(name, L.EG_XQ, rows=slice(q, q + 1))["gXq"]
-        assert _bits(one) == _bits(full[q:q + 1]), q
+        assert A.raw_bytes(one) == A.raw_bytes(full[q:q + 1]), q
 
 
 def test_forward_without_grad_is_what_it_was_and_counts_as_before():
     lib = _L().lib()
     Xq, Xdb, P, k, epsilon, eps_db, gU, *_ = E.grad_case("auto")
-    xq, xdb, p, e = _dev(Xq), _dev(Xdb), _dev(P), _dev(eps_db)
+    xq, xdb, p, e = A.dev(Xq), A.dev(Xdb), A.dev(P), A.dev(eps_db)
     q0, g0 = lib.gll_query_launches(), lib.gll_extend_grad_launches()
     U0, l0 = _G().extend(xq, xdb, p, k=k, epsilon=epsilon, eps_db=e)
     q1 = lib.gll_query_launches()
@@ -254,14 +245,14 @@ def test_forward_without_grad_is_what_it_was_and_counts_as_before():
     _L().check(lib.gll_extend(len(Xq), len(Xdb), k - 1, P.shape[1], idx.int().data_ptr(), d2.data_ptr(),
                               p.data_ptr(), e.data_ptr(), ct.c_float(0.0), Uc.data_ptr(), lc.data_ptr(),
                               st.data_ptr(), torch.cuda.current_stream().cuda_stream), "gll_extend")
-    assert _bits(Uc) == _bits(U0) and torch.equal(lc, l0)
+    assert A.raw_bytes(Uc) == A.raw_bytes(U0) and torch.equal(lc, l0)
     q2 = lib.gll_query_launches()
     U1, l1 = _G().extend(xq.clone().requires_grad_(True), xdb, p, k=k, epsilon=epsilon, eps_db=e)
     assert lib.gll_query_launches() - q2 == 4 and lib.gll_extend_grad_launches() == g0
-    assert U1.grad_fn is not None and _bits(U1) == _bits(U0) and torch.equal(l1, l0)
+    assert U1.grad_fn is not None and A.raw_bytes(U1) == A.raw_bytes(U0) and torch.equal(l1, l0)
     with torch.no_grad():
         U2, _ = _G().extend(xq.clone().requires_grad_(True), xdb, p, k=k, epsilon=epsilon, eps_db=e)
-    assert U2.grad_fn is None and _bits(U2) == _bits(U0)
+    assert U2.grad_fn is None and A.raw_bytes(U2) == A.raw_bytes(U0)
 
 
 # ------------------------------------------------------------------------------------------
@@ -280,8 +271,8 @@ def test_launches_per_what():
         assert lib.gll_query_launches() == q0
     # through autograd: Xq alone is one launch
     Xq, Xdb, P, k, epsilon, *_ = E.grad_case("fixed")
-    xq = _dev(Xq).requires_grad_(True)
-    Uq, _ = _G().extend(xq, _dev(Xdb), _dev(P), k=k, epsilon=epsilon)
+    xq = A.dev(Xq).requires_grad_(True)
+    Uq, _ = _G().extend(xq, A.dev(Xdb), A.dev(P), k=k, epsilon=epsilon)
     n0 = lib.gll_extend_grad_launches()
     Uq.sum().backward()
     assert lib.gll_extend_grad_launches() - n0 == 1
@@ -296,22 +287,22 @@ def test_zero_weight_sum_is_nan_in_its_own_rows_only():
     gfar = np.concatenate([gU, np.ones((1, gU.shape[1]))])
 
     def run(xq_np, g_np):
-        xq, xdb, p = (_dev(a).requires_grad_(True) for a in (xq_np, Xdb, P))
+        xq, xdb, p = (A.dev(a).requires_grad_(True) for a in (xq_np, Xdb, P))
         eps = torch.tensor(float(epsilon), dtype=torch.float64, device="cuda", requires_grad=True)
         Uq, _, st = _G().extend(xq, xdb, p, k=k, epsilon=eps, return_status=True)
-        (Uq * _dev(g_np)).sum().backward()
+        (Uq * A.dev(g_np)).sum().backward()
         return Uq, st, xq.grad, xdb.grad, p.grad, eps.grad
 
     Uq, st, gq, gdb, gp, ge = run(far, gfar)
     U0, _, gq0, gdb0, gp0, ge0 = run(Xq, gU)
     assert torch.isnan(Uq[-1]).all() and st.cpu()[_L().QST_ZERO_SUM] == 1
     assert torch.isnan(gq[-1]).all() and torch.isnan(ge).all() and torch.isfinite(ge0).all()
-    assert _bits(gq[:-1]) == _bits(gq0)
-    listed = _G().knn_query(_dev(far[-1:]), _dev(Xdb), k - 1)[0][0]
+    assert A.raw_bytes(gq[:-1]) == A.raw_bytes(gq0)
+    listed = _G().knn_query(A.dev(far[-1:]), A.dev(Xdb), k - 1)[0][0]
     mask = torch.zeros(len(Xdb), dtype=torch.bool, device="cuda")
     mask[listed] = True
     assert torch.isnan(gdb[mask]).all() and torch.isnan(gp[mask]).all()
-    assert _bits(gdb[~mask]) == _bits(gdb0[~mask]) and _bits(gp[~mask]) == _bits(gp0[~mask])
+    assert A.raw_bytes(gdb[~mask]) == A.raw_bytes(gdb0[~mask]) and A.raw_bytes(gp[~mask]) == A.raw_bytes(gp0[~mask])
     assert torch.isfinite(gdb0).all() and torch.isfinite(gp0).all()
 
 
@@ -328,7 +319,7 @@ def test_indices_out_of_range_are_not_followed():
     less = _stage(name, 15, rows=keep)
     assert got["status"].cpu()[_L().EGST_ZERO_SUM] == 2
     assert torch.isnan(got["gXq"][[3, 7]]).all() and torch.isnan(got["geps"]).all()
-    assert _bits(got["gXq"][keep]) == _bits(clean["gXq"][keep]) == _bits(less["gXq"])
+    assert A.raw_bytes(got["gXq"][keep]) == A.raw_bytes(clean["gXq"][keep]) == A.raw_bytes(less["gXq"])
     mask = torch.zeros(N, dtype=torch.bool, device="cuda")
     for q, i in ((3, 2), (7, 0)):
         rest = [c for c in range(idx.shape[1]) if c != i]
@@ -338,7 +329,7 @@ def test_indices_out_of_range_are_not_followed():
     for key in ("gXdb", "gP"):
         assert torch.isnan(got[key][mask]).all()
         assert torch.isfinite(got[key][~mask]).all()
-        assert _bits(got[key][~mask]) == _bits(less[key][~mask]), key
+        assert A.raw_bytes(got[key][~mask]) == A.raw_bytes(less[key][~mask]), key
 
 
 # ------------------------------------------------------------------------------------------
@@ -358,23 +349,23 @@ def _chain_data():
 def test_query_loss_reaches_the_graph_features_through_apply():
     F = _G().LaplaceLearningSparseHard
     X, Xq, lab, gU, base, C, kk = _chain_data()
-    Y = _dev(np.eye(C, dtype=np.float32)[lab[:base]])
+    Y = A.dev(np.eye(C, dtype=np.float32)[lab[:base]])
     tau, eps = 0.01, 2.0
-    x1 = _dev(X).requires_grad_(True)
+    x1 = A.dev(X).requires_grad_(True)
     U = F.apply(x1, Y, tau, eps, kk)
     P = torch.cat([Y.double(), U]).float()
-    Uq, _ = _G().extend(_dev(Xq), x1.detach(), P, k=kk, epsilon=eps)
-    (Uq * _dev(gU)).sum().backward()
+    Uq, _ = _G().extend(A.dev(Xq), x1.detach(), P, k=kk, epsilon=eps)
+    (Uq * A.dev(gU)).sum().backward()
     # by hand: gP of the extension, its unlabeled rows fed to apply's backward
-    x2 = _dev(X).requires_grad_(True)
+    x2 = A.dev(X).requires_grad_(True)
     U2 = F.apply(x2, Y, tau, eps, kk)
     P2 = torch.cat([Y.double(), U2.detach()]).float().requires_grad_(True)
-    Uq2, _ = _G().extend(_dev(Xq), x2.detach(), P2, k=kk, epsilon=eps)
-    (Uq2 * _dev(gU)).sum().backward()
+    Uq2, _ = _G().extend(A.dev(Xq), x2.detach(), P2, k=kk, epsilon=eps)
+    (Uq2 * A.dev(gU)).sum().backward()
     U2.backward(P2.grad[base:].double())
-    assert _bits(Uq) == _bits(Uq2)
+    assert A.raw_bytes(Uq) == A.raw_bytes(Uq2)
     assert torch.isfinite(x1.grad).all() and x1.grad.abs().max() > 0
-    assert _bits(x1.grad) == _bits(x2.grad)
+    assert A.raw_bytes(x1.grad) == A.raw_bytes(x2.grad)
 
 
 @pytest.mark.parametrize("epsilon", ["auto", 2.0])
@@ -382,17 +373,17 @@ def test_laplace_predict_passes_the_gradient_of_extend(epsilon):
     from graphlearninglayer_amd import utils
     X, Xq, lab, gU, base, C, kk = _chain_data()
     fit = utils.laplace_fit(X, lab[:base], knn_num=kk, epsilon=epsilon)
-    a = _dev(Xq).requires_grad_(True)
+    a = A.dev(Xq).requires_grad_(True)
     Ua, _ = utils.laplace_predict(fit, a, knn_num=kk)
-    (Ua * _dev(gU)).sum().backward()
-    b = _dev(Xq).requires_grad_(True)
+    (Ua * A.dev(gU)).sum().backward()
+    b = A.dev(Xq).requires_grad_(True)
     Ub, _ = _G().extend(b, fit.X, fit.P, k=kk, epsilon=epsilon, eps_db=fit.eps)
-    (Ub * _dev(gU)).sum().backward()
-    assert Ua.grad_fn is not None and _bits(Ua) == _bits(Ub) and _bits(a.grad) == _bits(b.grad)
+    (Ub * A.dev(gU)).sum().backward()
+    assert Ua.grad_fn is not None and A.raw_bytes(Ua) == A.raw_bytes(Ub) and A.raw_bytes(a.grad) == A.raw_bytes(b.grad)
     assert torch.isfinite(a.grad).all() and a.grad.abs().max() > 0
     # the fit's arrays take gradients when the caller asks for them
     fit2 = fit._replace(X=fit.X.clone().requires_grad_(True), P=fit.P.clone().requires_grad_(True))
-    Uc, _ = utils.laplace_predict(fit2, _dev(Xq), knn_num=kk)
-    (Uc * _dev(gU)).sum().backward()
+    Uc, _ = utils.laplace_predict(fit2, A.dev(Xq), knn_num=kk)
+    (Uc * A.dev(gU)).sum().backward()
     assert fit2.X.grad.shape == fit.X.shape and fit2.P.grad.shape == fit.P.shape
     assert torch.isfinite(fit2.X.grad).all() and fit2.P.grad.abs().max() > 0

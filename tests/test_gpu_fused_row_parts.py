@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from oracle import gll_oracle as O
+from tests import abi as A
 from tests.star_graphs import row_lengths, row_parts, star_points
 
 pytestmark = pytest.mark.gpu
@@ -29,14 +30,7 @@ TAU, EPS = 0.07, 1.0
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from graphlearninglayer_amd import _lib
-    _lib.lib()  # fail loudly when the HIP library is missing
-
-
-def _nan(*shape, dtype):
-    return torch.full(shape, float("nan"), dtype=dtype, device="cuda")
+    A.need_gpu()
 
 
 def _problem(n, d, base, flags=0):
@@ -49,30 +43,15 @@ def _run(X, Y, gbar, flags=0, knob=0, backward_calls=2):
     GLL_KNOB_GRAD_SPLIT = knob: [grad_X], [status words after each backward], [launches]."""
     from graphlearninglayer_amd import _lib
     from tests.launch_counts import counted
-    n, d = X.shape
-    base = Y.shape[0]
-    prob = _problem(n, d, base, flags)
-    lib = _lib.lib()
-    ws = torch.empty(lib.gll_workspace_bytes(ct.byref(prob)), dtype=torch.uint8, device="cuda")
-    U = _nan(n - base, 10, dtype=torch.float64)
-    Xd, Yd, Gd = (torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (X, Y, gbar))
-    s = torch.cuda.current_stream().cuda_stream
+    run = A.Run(X, Y, K, TAU, EPS, flags)
     grads, sts, ran = [], [], []
-    _lib.set_knob(_lib.KNOB_GRAD_SPLIT, knob)
-    try:
-        _lib.check(lib.gll_forward(ct.byref(prob), Xd.data_ptr(), Yd.data_ptr(), _lib.GLL_DT_F32,
-                                   ws.data_ptr(), U.data_ptr(), s), "gll_forward")
+    with A.knobs({_lib.KNOB_GRAD_SPLIT: knob}):
+        run.forward()
         for _ in range(backward_calls):
-            gx = _nan(n, d, dtype=torch.float32)
             with counted() as got:
-                _lib.check(lib.gll_backward(ct.byref(prob), Xd.data_ptr(), None, 0, ws.data_ptr(),
-                                            Gd.data_ptr(), _lib.GLL_DT_F64, gx.data_ptr(), s),
-                           "gll_backward")
-            grads.append(gx.cpu().numpy())
-            sts.append(ws[: 4 * _lib.ST_NWORDS].view(torch.int32).cpu().tolist())
+                grads.append(run.backward(gbar, labels=False))
+            sts.append(run.status())
             ran.append(got.counts)
-    finally:
-        _lib.set_knob(_lib.KNOB_GRAD_SPLIT, 0)
     return grads, sts, ran
 
 

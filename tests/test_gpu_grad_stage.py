@@ -27,128 +27,70 @@ The hub row of 149 edges: 0.017 of its bound in the fused kernel, 0.008 through 
 pass.  Every launch count equalled route()'s, every fused case ran the fused kernel, and no
 element was left NaN: no defect found.  The whole file runs in 5 s.
 """
-import ctypes as ct
 import time
 
 import numpy as np
 import pytest
-import torch
 
+from graphlearninglayer_amd import _lib as L
+from tests import abi as A
 from tests import grad_ref as R
 from tests.launch_counts import counted
 
 pytestmark = pytest.mark.gpu
-
-
-def _lib():
-    from graphlearninglayer_amd import _lib
-    return _lib
-
-
-def _gll():
-    from graphlearninglayer_amd import GLL
-    return GLL
-
 
 _worst = {}     # family -> [cases, worst err/bound, worst err/max|grad|, seconds]
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    _lib().lib()  # fail loudly when the HIP library is missing
+    A.need_gpu()
     yield
     for fam, (cnt, rb, rg, sec) in sorted(_worst.items()):
         print(f"\ngrad stage {fam}: {cnt} cases, worst err/bound {rb:.4f}, worst err/max|grad| "
               f"{rg:.2e}, {sec:.1f} s")
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 class Session:
-    """One case on the device: the features of its B graphs (optionally 4 bytes off 16-B
-    alignment), B workspace blocks, one forward; then backwards into NaN-filled outputs."""
+    """One case on the device (tests/abi.py Run): the features of its B graphs (optionally 4
+    bytes off 16-B alignment), B workspace blocks, one forward; then backwards into NaN-filled
+    outputs."""
 
     def __init__(self, case):
-        L = _lib()
         self.case = c = case
         xy = [R.features(c, g) for g in range(c.B)]
         self.Xh = np.stack([x for x, _ in xy])
         self.Yh = np.stack([y for _, y in xy])
         self.gb = np.stack([R.gbar(c, g) for g in range(c.B)])
-        buf = torch.empty(self.Xh.size + 4, dtype=torch.float32, device="cuda")
-        assert buf.data_ptr() % 16 == 0
-        off = 0 if c.aligned else 1
-        self.X = buf[off: off + self.Xh.size].view(c.B, c.n, c.d)
-        self.X.copy_(torch.from_numpy(self.Xh))
-        assert (self.X.data_ptr() % 16 == 0) == c.aligned
-        self.Y = torch.from_numpy(self.Yh).cuda()
-        self.wb = L.lib().gll_workspace_bytes(ct.byref(self.problem()))
-        assert self.wb > 0
-        self.ws = torch.empty(c.B * self.wb, dtype=torch.uint8, device="cuda")
-        self.U = torch.full((c.B, c.m, c.C), float("nan"), dtype=torch.float64, device="cuda")
-        p = self.problem()
-        if c.B == 1:
-            rc = L.lib().gll_forward(ct.byref(p), self.X.data_ptr(), self.Y.data_ptr(),
-                                     L.GLL_DT_F32, self.ws.data_ptr(), self.U.data_ptr(), _stream())
-        else:
-            rc = L.lib().gll_forward_batched(ct.byref(p), c.B, self.X.data_ptr(), self.Y.data_ptr(),
-                                             L.GLL_DT_F32, self.ws.data_ptr(), self.U.data_ptr(),
-                                             _stream())
-        L.check(rc, "gll_forward")
-
-    def problem(self):
-        c = self.case
-        return _gll().make_problem(c.n, c.d, c.base, c.C, c.K, R.TAU, c.eps, flags=c.flags)
+        one = c.B == 1
+        self.run = A.Run(self.Xh[0] if one else self.Xh, self.Yh[0] if one else self.Yh, c.K, R.TAU,
+                         c.eps, c.flags, aligned=c.aligned)
+        self.U = self.run.forward().reshape(c.B, c.m, c.C)
 
     def backward(self, g_dtype):
         """(grad_X B x n x d from a NaN-filled buffer, the launches bracketed)."""
-        L = _lib()
         c = self.case
-        dt = L.GLL_DT_F32 if g_dtype == "f32" else L.GLL_DT_F64
-        gd = torch.from_numpy(np.ascontiguousarray(
-            self.gb, dtype=np.float32 if g_dtype == "f32" else np.float64)).cuda()
-        gx = torch.full((c.B, c.n, c.d), float("nan"), dtype=torch.float32, device="cuda")
-        p = self.problem()
         with counted() as got:
-            if c.B == 1:
-                rc = L.lib().gll_backward(ct.byref(p), self.X.data_ptr(), self.Y.data_ptr(),
-                                          L.GLL_DT_F32, self.ws.data_ptr(), gd.data_ptr(), dt,
-                                          gx.data_ptr(), _stream())
-            else:
-                rc = L.lib().gll_backward_batched(ct.byref(p), c.B, self.X.data_ptr(),
-                                                  self.ws.data_ptr(), gd.data_ptr(), dt,
-                                                  gx.data_ptr(), _stream())
-            L.check(rc, "gll_backward")
-        return gx.cpu().numpy(), got
-
-    def _arr(self, ptr, count, dtype):
-        off = ptr - self.ws.data_ptr()
-        return self.ws[off: off + 4 * count].view(dtype).cpu().numpy()
+            gx = self.run.backward(self.gb, L.GLL_DT_F32 if g_dtype == "f32" else L.GLL_DT_F64)
+        return gx.reshape(c.B, c.n, c.d), got
 
     def stage(self, g):
         """The float64 closed form on graph g's workspace arrays as the backward left them."""
-        L = _lib()
-        c = self.case
-        v = L.View()
-        p = self.problem()
-        L.check(L.lib().gll_workspace_view(ct.byref(p), self.ws.data_ptr() + g * self.wb,
-                                           ct.byref(v)), "gll_workspace_view")
+        c, run = self.case, self.run
+        v = run.view(g)
         K = min(c.K, c.n)
-        i32, f32 = torch.int32, torch.float32
-        rs, rl = self._arr(v.row_start, c.n, i32), self._arr(v.row_len, c.n, i32)
+        i32, f32 = np.int32, np.float32
+        a = lambda ptr, count, dt: run.array(ptr, count, dt, g)
+        rs, rl = a(v.row_start, c.n, i32), a(v.row_len, c.n, i32)
         E = int((rs.astype(np.int64) + rl).max())
-        U32 = self._arr(v.U32, c.m * c.C, f32).reshape(c.m, c.C)
-        wadj = self._arr(v.wadj, c.m * c.C, f32).reshape(c.m, c.C)
+        U32 = a(v.U32, c.m * c.C, f32).reshape(c.m, c.C)
+        wadj = a(v.wadj, c.m * c.C, f32).reshape(c.m, c.C)
         assert np.isfinite(U32).all() and np.isfinite(wadj).all()
-        st = self._arr(v.status, L.ST_NWORDS, i32)
+        st = a(v.status, L.ST_NWORDS, i32)
         assert st[L.ST_SOLVE_FAILED] == 0 and st[L.ST_BWD_NONCONV] == 0
         return R.grad_stage(
-            rs, rl, self._arr(v.col, E, i32), self._arr(v.w, E, f32), self._arr(v.d2, E, f32),
-            self._arr(v.eps, c.n, f32), self._arr(v.knn_idx, c.n * K, i32).reshape(c.n, K),
+            rs, rl, a(v.col, E, i32), a(v.w, E, f32), a(v.d2, E, f32), a(v.eps, c.n, f32),
+            a(v.knn_idx, c.n * K, i32).reshape(c.n, K),
             np.concatenate([self.Yh[g], U32]), np.concatenate([np.zeros_like(self.Yh[g]), wadj]),
             self.Xh[g], c.auto, None if c.auto else np.float32(c.eps)), rl
 
@@ -226,7 +168,7 @@ def test_fused_backward_gradient_role(name):
     if case.feat == "hub":
         assert longest > 128
     if case.feat == "one_class":
-        P = np.concatenate([ses.Yh[0], ses.U[0].cpu().numpy()])
+        P = np.concatenate([ses.Yh[0], ses.U[0]])
         assert (P.argmax(axis=1) == 0).all()
 
 

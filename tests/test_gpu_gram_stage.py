@@ -50,6 +50,8 @@ import numpy as np
 import pytest
 import torch
 
+from graphlearninglayer_amd import _lib as L
+from tests import abi as A
 from tests import gram_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -60,21 +62,9 @@ _sessions = {}
 _model_cache = {}
 
 
-def _lib():
-    from graphlearninglayer_amd import _lib
-    return _lib
-
-
-def _gll():
-    from graphlearninglayer_amd import GLL
-    return GLL
-
-
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    _lib().lib()  # fail loudly when the HIP library is missing
+    A.need_gpu()
     _record["t0"] = time.perf_counter()
     yield
     _sessions.clear()
@@ -85,10 +75,6 @@ def _need_gpu():
             cnt, worst = _stats[fam].get(q, (0, 0.0))
             if cnt:
                 print(f"gram stage {fam:8s} {q:8s}: {cnt:10d} elements, worst err/bound {worst:.4f}")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _cus():
@@ -102,67 +88,49 @@ BASE, CLASSES, TAU = 8, 2, 0.1     # batches go through gll_forward_batched: a f
 
 
 class Session:
-    """One case on the device: its B graphs (or the graphs `graphs`, a batch of that many), B
-    workspace blocks of 0xFF bytes, one graph build with the case's flags and knobs."""
+    """One case on the device (tests/abi.py Run): its B graphs (or the graphs `graphs`, a batch of
+    that many), B workspace blocks of 0xFF bytes, one graph build with the case's flags and
+    knobs."""
 
     def __init__(self, case, graphs=None, order=False):
-        L = _lib()
         self.case = case
         self.graphs = list(range(case.B)) if graphs is None else list(graphs)
         B = self.B = len(self.graphs)
-        n, d = case.n, case.d
+        n = case.n
         self.Xh = [R.features(case, g) for g in self.graphs]
-        flat = np.concatenate([x.ravel() for x in self.Xh])
-        buf = torch.zeros(flat.size + 4, dtype=torch.float32, device="cuda")
-        assert buf.data_ptr() % 16 == 0
-        o = 1 if case.misalign else 0
-        buf[o: o + flat.size] = torch.from_numpy(flat).cuda()
-        self.buf, self.xptr = buf, buf.data_ptr() + 4 * o
         single = case.B == 1
-        self.p = p = _gll().make_problem(n, d, 0 if single else BASE, 1 if single else CLASSES,
-                                         case.K, TAU, 1.0, flags=case.flags)
-        self.wb = wb = L.lib().gll_workspace_bytes(ct.byref(p))
-        assert wb > 0
-        self.ws = torch.full((B * wb,), 0xFF, dtype=torch.uint8, device="cuda")
+        if single:
+            assert B == 1
+            X, Y = self.Xh[0], None
+        else:
+            X, Y = np.stack(self.Xh), np.zeros((B, BASE, CLASSES), dtype=np.float32)
+            Y[:, np.arange(BASE), np.arange(BASE) % CLASSES] = 1.0
+        run = A.Run(X, Y, case.K, TAU, 1.0, case.flags, C=1 if single else None,
+                    aligned=not case.misalign, ws_fill=0xFF)
         out = (ct.c_int32 * L.GRAM_ROUTE_WORDS)()
-        try:
-            L.set_knob(L.KNOB_GRAM_TILE, case.tile)
-            L.set_knob(L.KNOB_GRAM_TAIL, case.tail)
-            L.check(L.lib().gll_gram_route(ct.byref(p), B, int(not case.misalign), _cus(), out),
-                    "gll_gram_route")
+        with A.knobs({L.KNOB_GRAM_TILE: case.tile, L.KNOB_GRAM_TAIL: case.tail}):
+            L.check(L.lib().gll_gram_route(ct.byref(run.problem()), B, int(not case.misalign),
+                                           _cus(), out), "gll_gram_route")
             self.route = R.Route(*out)
             if single:
-                assert B == 1
-                rc = L.lib().gll_graph(ct.byref(p), self.xptr, self.ws.data_ptr(), _stream())
+                run.graph()
             else:
-                Y = torch.zeros(B, BASE, CLASSES, dtype=torch.float32, device="cuda")
-                Y[:, torch.arange(BASE), torch.arange(BASE) % CLASSES] = 1.0
-                U = torch.zeros(B, n - BASE, CLASSES, dtype=torch.float64, device="cuda")
-                rc = L.lib().gll_forward_batched(ct.byref(p), B, self.xptr, Y.data_ptr(),
-                                                 L.GLL_DT_F32, self.ws.data_ptr(), U.data_ptr(),
-                                                 _stream())
-            L.check(rc, "graph build")
-            torch.cuda.synchronize()
-        finally:
-            L.set_knob(L.KNOB_GRAM_TILE, 0)
-            L.set_knob(L.KNOB_GRAM_TAIL, 0)
-        v = self.view = L.KnnView()
-        L.check(L.lib().gll_workspace_knn_view(ct.byref(p), B, self.ws.data_ptr(), ct.byref(v)),
-                "gll_workspace_knn_view")
+                run.forward()
+        v = run.knn_view()
         rt = self.route
         assert (v.planes, v.d2_half, v.rows, v.ldD, v.dp) == \
             (rt.planes, rt.H, case.buffer_rows().size, (n + 3) & ~3, case.dp)
         esz = 2 if rt.H else 4
         nb = ((rt.planes - 1) * v.plane_stride + v.rows * v.ldD) * esz
-        raw = self._region(v.D2, nb).view(np.float16 if rt.H else np.float32)
+        raw = run.blocks(v.D2, nb).view(np.float16 if rt.H else np.float32)
         self.D2 = np.stack([raw[:, q * v.plane_stride: q * v.plane_stride + v.rows * v.ldD]
                             .reshape(B, v.rows, v.ldD)[:, :, :n] for q in range(rt.planes)], axis=1)
         self.outs = []
         if rt.presplit:
-            xhi = self._region(v.xhi, n * v.dp * 2).view(np.uint16).reshape(B, n, v.dp)
-            xlo = self._region(v.xlo, n * v.dp * 2).view(np.uint16).reshape(B, n, v.dp)
-            xnrm = self._region(v.xnrm, n * 4).view(np.float32)
-        scale = self._region(v.d2_scale, 4).view(np.float32)[:, 0] if rt.H else None
+            xhi = run.blocks(v.xhi, n * v.dp * 2).view(np.uint16).reshape(B, n, v.dp)
+            xlo = run.blocks(v.xlo, n * v.dp * 2).view(np.uint16).reshape(B, n, v.dp)
+            xnrm = run.blocks(v.xnrm, n * 4).view(np.float32)
+        scale = run.blocks(v.d2_scale, 4).view(np.float32)[:, 0] if rt.H else None
         for q in range(B):
             o = {"D2": self.D2[q], "scale": None if scale is None else scale[q]}
             if rt.presplit:
@@ -170,15 +138,8 @@ class Session:
             self.outs.append(o)
         if order:
             assert v.order == 1
-            self.pid = self._region(v.pid, n * 4).view(np.int32)[0]
-            self.perm = self._region(v.perm, n * 4).view(np.int32)[0]
-        del self.ws
-
-    def _region(self, ptr, nbytes):
-        """[B][nbytes] bytes at `ptr` of block 0 and at the same offset of every other block."""
-        off = ptr - self.ws.data_ptr()
-        assert 0 <= off and off + nbytes <= self.wb
-        return self.ws.view(self.B, self.wb)[:, off: off + nbytes].contiguous().cpu().numpy()
+            self.pid = run.blocks(v.pid, n * 4).view(np.int32)[0]
+            self.perm = run.blocks(v.perm, n * 4).view(np.int32)[0]
 
 
 def _session(case):
@@ -212,7 +173,7 @@ def _hold(case, like=None):
     if like is not None:
         ref = _session(like)
         assert all(np.array_equal(x, y) for x, y in zip(ses.Xh, ref.Xh))
-        assert np.array_equal(_bits(ses.D2), _bits(ref.D2)), f"{case.name} differs from {like.name}"
+        assert np.array_equal(A.bits(ses.D2), A.bits(ref.D2)), f"{case.name} differs from {like.name}"
         qs = qs[:3] + qs[-10:]
     outs = [ses.outs[q] for q in qs]
     if want.H:       # the halves against the fp32 run of the same inputs
@@ -230,10 +191,6 @@ def _hold(case, like=None):
     print(f"{case.name} {sorted(R.kernels(want))}: " +
           ", ".join(f"{k} {c} el. {w:.4f}" for k, (c, w) in got.items() if c))
     return ses, got, len(qs)
-
-
-def _bits(a):
-    return a.view(np.uint16 if a.dtype == np.float16 else np.uint32)
 
 
 def _like(case):
@@ -287,11 +244,11 @@ def test_graph_of_a_batch_is_the_graph_alone(name):
         for g in ses.graphs:     # the same features: graph g of the batch, alone
             solo = Session(dataclasses.replace(case, B=1), graphs=[g])
             assert np.array_equal(solo.Xh[0], ses.Xh[g]) and solo.route == ses.route
-            assert np.array_equal(_bits(solo.D2[0]), _bits(ses.D2[g]))
+            assert np.array_equal(A.bits(solo.D2[0]), A.bits(ses.D2[g]))
         return
     rev = Session(case, graphs=ses.graphs[::-1])
     assert rev.route == ses.route
-    assert np.array_equal(_bits(rev.D2[::-1]), _bits(ses.D2))
+    assert np.array_equal(A.bits(rev.D2[::-1]), A.bits(ses.D2))
     if ses.route.H:
         assert [o["scale"] for o in rev.outs[::-1]] == [o["scale"] for o in ses.outs]
 
@@ -302,12 +259,12 @@ def test_tail_settings_give_bitwise_equal_d2():
     assert (a.route.tail, a.route.sub, b.route.tail, c.route.tail, c.route.sub) == (14, 16, 0, 14, 4)
     assert all(np.array_equal(x, y) for x, y in zip(a.Xh, b.Xh))
     for other in (b, c):
-        assert np.array_equal(_bits(a.D2), _bits(other.D2))
+        assert np.array_equal(A.bits(a.D2), A.bits(other.D2))
         assert [o["scale"] for o in a.outs] == [o["scale"] for o in other.outs]
     # and on fp32 storage (gram_pk<false, 64> and gram_pk<false, 128> against gram_pk2<false>)
     fa, fb, fc = (_session(R.f32_twin(R.CASES[f"pk2_tail{k}_B90_512x192"])) for k in (0, 1, 2))
     for other in (fb, fc):
-        assert np.array_equal(_bits(fa.D2), _bits(other.D2))
+        assert np.array_equal(A.bits(fa.D2), A.bits(other.D2))
 
 
 @pytest.mark.parametrize("flags", [0, R.FLAG_D2_F32], ids=["fp16", "fp32"])
@@ -319,10 +276,10 @@ def test_128_tiles_and_256_tiles_give_bitwise_equal_d2(flags):
     c128 = dataclasses.replace(c256, tile=128, fam=R.PK, name=f"pk2_B43_300x100_t128/{flags}")
     a, b = _session(c256), _session(c128)
     assert (a.route.family, b.route.family) == (R.PK2, R.PK) and a.route.H == b.route.H
-    assert np.array_equal(_bits(a.D2), _bits(b.D2))
+    assert np.array_equal(A.bits(a.D2), A.bits(b.D2))
     for k in ("xhi", "xlo", "xnrm"):
-        assert all(np.array_equal(_bits(x[k]) if k == "xnrm" else x[k],
-                                  _bits(y[k]) if k == "xnrm" else y[k])
+        assert all(np.array_equal(A.bits(x[k]) if k == "xnrm" else x[k],
+                                  A.bits(y[k]) if k == "xnrm" else y[k])
                    for x, y in zip(a.outs, b.outs))
 
 

@@ -23,6 +23,7 @@ import torch
 
 from graphlearninglayer_amd.synth import seeded_gbar
 from oracle import gll_oracle as O
+from tests import abi as A
 from tests import ingest_ref as IR
 from tests.param_grad_ref import param_grads
 
@@ -48,20 +49,13 @@ def _LL():
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    _L().lib()  # fail loudly when the HIP library is missing
+    A.need_gpu()
     yield
     try:
         with open(os.path.join(ROOT, "profiles", "nl01_parity.json"), "w") as fh:
             json.dump(PARITY, fh, indent=1, sort_keys=True)
     except OSError:
         pass
-
-
-def _dev(a, dtype=None):
-    t = torch.from_numpy(np.array(a, order="C")).cuda()   # a copy: the cases are read-only
-    return t if dtype is None else t.to(dtype)
 
 
 def _record(tag, eU, eg):
@@ -74,26 +68,14 @@ def _record(tag, eU, eg):
 # ------------------------------------------------------------------------------------------------
 def _stage_run(X, nbr, epsilon):
     """gll_graph_lists on a 0xFF workspace: the arrays of gll_workspace_view on the host."""
-    L, G = _L(), _G()
-    n, d = X.shape
-    K = nbr.shape[1] + 1
-    p = G.make_problem(n, d, 0, 1, K, 0.0, epsilon, flags=L.FLAG_KNN_GIVEN)
-    nb = L.lib().gll_workspace_bytes(ct.byref(p))
-    assert nb > 0
-    ws = torch.full((nb,), 0xFF, dtype=torch.uint8, device="cuda")
-    Xd = _dev(X)
-    nd = _dev(nbr, torch.int32)
-    L.check(L.lib().gll_graph_lists(ct.byref(p), Xd.data_ptr(), nd.data_ptr(), ws.data_ptr(),
-                                    torch.cuda.current_stream().cuda_stream), "gll_graph_lists")
-    torch.cuda.synchronize()
-    v = L.View()
-    L.check(L.lib().gll_workspace_view(ct.byref(p), ws.data_ptr(), ct.byref(v)), "view")
-    host = ws.cpu().numpy()
+    L = _L()
+    n, K = X.shape[0], nbr.shape[1] + 1
+    run = A.Run(X, None, K, 0.0, epsilon, L.FLAG_KNN_GIVEN, C=1, ws_fill=0xFF, neighbors=nbr)
+    run.graph()
+    v, host = run.view(), run.host_copy()
 
     def arr(ptr, count, dtype):
-        off = ptr - ws.data_ptr()
-        assert 0 <= off and off + count * np.dtype(dtype).itemsize <= nb
-        return host[off: off + count * np.dtype(dtype).itemsize].view(dtype).copy()
+        return run.array(ptr, count, dtype, snapshot=host).copy()
 
     start, length = arr(v.row_start, n, np.int32), arr(v.row_len, n, np.int32)
     span = int((start.astype(np.int64) + length).max())
@@ -199,7 +181,7 @@ def test_oracle_parity_on_shuffled_lists(config, eps, tau):
     X, Y, nbr, k = IR.layer_case(config)
     assert IR.components(nbr) == 1 and Y.shape[0] > 0
     Uo, go, _, gbar = _oracle(config, eps, tau)
-    U, gX = _apply(_dev(X), _dev(Y), _dev(nbr), tau, eps, k, _dev(gbar))
+    U, gX = _apply(A.dev(X), A.dev(Y), A.dev(nbr), tau, eps, k, A.dev(gbar))
     eU, eg = O.rel_err(U.cpu().numpy(), Uo), O.rel_err(gX.cpu().numpy(), go)
     _record(f"{config}_eps{eps}_tau{tau}", eU, eg)
     assert eU <= TOL and eg <= TOL, (eU, eg)
@@ -210,11 +192,11 @@ def test_self_column_and_int32_lists_are_the_same_call():
     n x (k - 1), int32 or int64, on the host or the device: bitwise one result."""
     X, Y, nbr, k = IR.layer_case("plumbing")
     _, _, _, gbar = _oracle("plumbing", "auto", 0.07)
-    Xd, Yd, gd = _dev(X), _dev(Y), _dev(gbar)
-    U0, g0 = _apply(Xd, Yd, _dev(nbr), 0.07, "auto", k, gd)
-    for other in (_dev(IR.with_self(nbr)), _dev(nbr, torch.int32),
+    Xd, Yd, gd = A.dev(X), A.dev(Y), A.dev(gbar)
+    U0, g0 = _apply(Xd, Yd, A.dev(nbr), 0.07, "auto", k, gd)
+    for other in (A.dev(IR.with_self(nbr)), A.dev(nbr, torch.int32),
                   torch.from_numpy(IR.with_self(nbr).astype(np.int32)),
-                  _dev(IR.with_self(nbr))[:, 1:]):            # not contiguous
+                  A.dev(IR.with_self(nbr))[:, 1:]):            # not contiguous
         U1, g1 = _apply(Xd, Yd, other, 0.07, "auto", k, gd)
         assert torch.equal(U0, U1) and torch.equal(g0, g1)
 
@@ -228,10 +210,10 @@ def test_batch_of_three_is_bitwise_the_single_calls():
         Xs.append(X), Ys.append(one_hot(lab[: c["base"]])), Ns.append(IR.approx_lists(X, c["k"], seed))
     gbar = np.stack([seeded_gbar(c["batch"], 10, seed=s) for s in (5, 6, 7)])
     for eps in (1.0, "auto"):
-        Ub, gb = _apply(_dev(np.stack(Xs)), _dev(np.stack(Ys)), _dev(np.stack(Ns)), 0.07, eps,
-                        c["k"], _dev(gbar))
+        Ub, gb = _apply(A.dev(np.stack(Xs)), A.dev(np.stack(Ys)), A.dev(np.stack(Ns)), 0.07, eps,
+                        c["k"], A.dev(gbar))
         for b in range(3):
-            U1, g1 = _apply(_dev(Xs[b]), _dev(Ys[b]), _dev(Ns[b]), 0.07, eps, c["k"], _dev(gbar[b]))
+            U1, g1 = _apply(A.dev(Xs[b]), A.dev(Ys[b]), A.dev(Ns[b]), 0.07, eps, c["k"], A.dev(gbar[b]))
             assert torch.equal(Ub[b], U1) and torch.equal(gb[b], g1), (eps, b)
         Uo, st = O.forward(Xs[1], Ys[1], 0.07, eps, c["k"], knn=(IR.with_self(Ns[1]), None))
         eU = O.rel_err(Ub[1].cpu().numpy(), Uo)
@@ -245,13 +227,13 @@ def test_normalize_and_bf16_features():
     unit_features(Z) bitwise, which is held to the oracle on those rows."""
     G = _G()
     X, Y, nbr, k = IR.layer_case("plumbing")
-    gbar = _dev(seeded_gbar(64, 10))
-    Z = _dev(X * 3.0).to(torch.bfloat16)
+    gbar = A.dev(seeded_gbar(64, 10))
+    Z = A.dev(X * 3.0).to(torch.bfloat16)
     Xh, rnorm = G.unit_features(Z, True)
     Zt = Z.clone().requires_grad_(True)
-    U = _LL().apply(Zt, _dev(Y), 0.07, "auto", k, True, neighbors=_dev(nbr))
+    U = _LL().apply(Zt, A.dev(Y), 0.07, "auto", k, True, neighbors=A.dev(nbr))
     (gZ,) = torch.autograd.grad(U, Zt, gbar)
-    U1, gX1 = _apply(Xh, _dev(Y), _dev(nbr), 0.07, "auto", k, gbar)
+    U1, gX1 = _apply(Xh, A.dev(Y), A.dev(nbr), 0.07, "auto", k, gbar)
     assert torch.equal(U.detach(), U1)
     assert gZ.dtype == torch.bfloat16
     assert torch.equal(gZ, G.unit_features_backward(gX1, Xh, rnorm, torch.bfloat16, True))
@@ -267,12 +249,12 @@ def test_label_tau_and_epsilon_gradients():
     X, Y, nbr, k = IR.layer_case("plumbing")
     Uo, go, st, gbar = _oracle("plumbing", 1.0, 0.07)
     ref = param_grads(st, gbar)
-    Xt = _dev(X).requires_grad_(True)
-    Yt = _dev(Y).requires_grad_(True)
+    Xt = A.dev(X).requires_grad_(True)
+    Yt = A.dev(Y).requires_grad_(True)
     tt = torch.tensor(0.07, dtype=torch.float64, device="cuda", requires_grad=True)
     et = torch.tensor(1.0, dtype=torch.float64, device="cuda", requires_grad=True)
-    U = _LL().apply(Xt, Yt, tt, et, k, neighbors=_dev(nbr))
-    gX, gY, gt, ge = torch.autograd.grad(U, (Xt, Yt, tt, et), _dev(gbar))
+    U = _LL().apply(Xt, Yt, tt, et, k, neighbors=A.dev(nbr))
+    gX, gY, gt, ge = torch.autograd.grad(U, (Xt, Yt, tt, et), A.dev(gbar))
     eU, eg = O.rel_err(U.detach().cpu().numpy(), Uo), O.rel_err(gX.cpu().numpy(), go)
     eY = O.rel_err(gY.cpu().numpy(), ref.grad_Y)
     e_tau = abs(float(gt) - ref.grad_tau) / ref.tau_terms
@@ -303,7 +285,7 @@ def test_hub_column_against_the_oracle():
     for eps in (1.0, "auto"):
         Uo, st = O.forward(X, Y, 0.07, eps, 5, knn=(IR.with_self(nbr), None))
         go = O.backward(st, gbar)
-        U, gX = _apply(_dev(X), _dev(Y), _dev(nbr), 0.07, eps, 5, _dev(gbar))
+        U, gX = _apply(A.dev(X), A.dev(Y), A.dev(nbr), 0.07, eps, 5, A.dev(gbar))
         eU, eg = O.rel_err(U.cpu().numpy(), Uo), O.rel_err(gX.cpu().numpy(), go)
         _record(f"hub600_eps{eps}_tau0.07", eU, eg)
         assert eU <= TOL and eg <= TOL, (eps, eU, eg)
@@ -331,10 +313,10 @@ def test_exact_lists_reproduce_the_search(k):
     tie = ((dl[:, 1:] - dl[:, :-1]) <= sep * dl[:, 1:]).any(axis=1)
     assert tie.sum() <= 5, tie.sum()                  # NS: 4 rows at k = 10, none at k = 100
     gbar = seeded_gbar(c["batch"], 10)
-    Xd, Yd, gd = _dev(X), _dev(Y), _dev(gbar)
+    Xd, Yd, gd = A.dev(X), A.dev(Y), A.dev(gbar)
     for eps in (1.0, "auto"):
         gs = G.device_graph(Xd, k, eps)
-        gl = G.device_graph(Xd, k, eps, neighbors=_dev(nbr))
+        gl = G.device_graph(Xd, k, eps, neighbors=A.dev(nbr))
         assert (gl["knn_idx"][:, 1:].cpu().numpy() == nbr).all()
         si = gs["knn_idx"].cpu().numpy()
         assert (si[~tie, 1:] == nbr[~tie]).all()
@@ -354,7 +336,7 @@ def test_exact_lists_reproduce_the_search(k):
         Xt = Xd.clone().requires_grad_(True)
         Us = _LL().apply(Xt, Yd, 0.07, eps, k)
         (gXs,) = torch.autograd.grad(Us, Xt, gd)
-        Ul, gXl = _apply(Xd, Yd, _dev(nbr), 0.07, eps, k, gd)
+        Ul, gXl = _apply(Xd, Yd, A.dev(nbr), 0.07, eps, k, gd)
         eU = O.rel_err(Ul.cpu().numpy(), Us.detach().cpu().numpy())
         eg = O.rel_err(gXl.cpu().numpy(), gXs.cpu().numpy())
         Uo, st = O.forward(X, Y, 0.07, eps, k, knn=(IR.with_self(nbr), None))
@@ -370,9 +352,9 @@ def test_exact_lists_reproduce_the_search(k):
 @pytest.mark.parametrize("eps", [1.0, "auto"])
 def test_native_and_python_paths_agree_bitwise(eps):
     X, Y, nbr, k = IR.layer_case("plumbing")
-    gbar = _dev(seeded_gbar(64, 10))
-    a = _apply(_dev(X), _dev(Y), _dev(nbr), 0.07, eps, k, gbar)
-    b = _apply(_dev(X), _dev(Y), _dev(nbr), 0.07, eps, k, gbar, fn="apply_python")
+    gbar = A.dev(seeded_gbar(64, 10))
+    a = _apply(A.dev(X), A.dev(Y), A.dev(nbr), 0.07, eps, k, gbar)
+    b = _apply(A.dev(X), A.dev(Y), A.dev(nbr), 0.07, eps, k, gbar, fn="apply_python")
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
 
 
@@ -380,12 +362,12 @@ def test_native_and_python_paths_agree_bitwise(eps):
 def test_two_runs_are_bitwise_equal(config):
     G = _G()
     X, Y, nbr, k = IR.layer_case(config)
-    gbar = _dev(seeded_gbar(X.shape[0] - Y.shape[0], 10))
+    gbar = A.dev(seeded_gbar(X.shape[0] - Y.shape[0], 10))
     for eps in (1.0, "auto"):
         runs = []
         for _ in range(2):
-            g = G.device_graph(_dev(X), k, eps, neighbors=_dev(nbr))
-            U, gX = _apply(_dev(X), _dev(Y), _dev(nbr), 0.07, eps, k, gbar)
+            g = G.device_graph(A.dev(X), k, eps, neighbors=A.dev(nbr))
+            U, gX = _apply(A.dev(X), A.dev(Y), A.dev(nbr), 0.07, eps, k, gbar)
             runs.append((g["knn_idx"].clone(), g["knn_d2"].clone(), g["eps"].clone(), U, gX))
         for x, y in zip(*runs):
             assert torch.equal(x, y)
@@ -397,10 +379,10 @@ def test_two_runs_are_bitwise_equal(config):
 def test_heads_equal_apply_followed_by_the_torch_formulas():
     G = _G()
     X, Y, nbr, k = IR.layer_case("plumbing")
-    Xd, Yd, nd = _dev(X), _dev(Y), _dev(nbr)
+    Xd, Yd, nd = A.dev(X), A.dev(Y), A.dev(nbr)
     m, C = 64, 10
     rng = np.random.default_rng(11)
-    tgt = _dev(rng.integers(0, C, size=m))
+    tgt = A.dev(rng.integers(0, C, size=m))
     for eps in (1.0, "auto"):
         Xa = Xd.clone().requires_grad_(True)
         Ua = _LL().apply(Xa, Yd, 0.07, eps, k, neighbors=nd)
@@ -444,11 +426,11 @@ def test_frozen_graph_sign_gradient_steps():
     sign-gradient steps, each against the oracle on the same lists."""
     G = _G()
     X, Y, _, k = IR.layer_case("plumbing")
-    Xd, Yd = _dev(X), _dev(Y)
+    Xd, Yd = A.dev(X), A.dev(Y)
     knn_idx = G.device_graph(Xd, k, "auto")["knn_idx"].clone()     # n x k, self first
     ind = knn_idx.cpu().numpy().astype(np.int64)
     gbar = seeded_gbar(64, 10)
-    gd = _dev(gbar)
+    gd = A.dev(gbar)
     Xp = Xd.clone()
     for step in range(3):
         U, gX = _apply(Xp, Yd, knn_idx, 0.07, "auto", k, gd)
@@ -468,7 +450,7 @@ def test_frozen_graph_sign_gradient_steps():
 def test_device_graph_matches_the_oracles_csr(eps):
     G = _G()
     X, _, nbr, k = IR.layer_case("plumbing")
-    g = G.device_graph(_dev(X), k, eps, neighbors=_dev(nbr))
+    g = G.device_graph(A.dev(X), k, eps, neighbors=A.dev(nbr))
     Xd = X.astype(np.float64)
     ind = IR.with_self(nbr)
     dist = np.sqrt(((Xd[:, None, :] - Xd[ind]) ** 2).sum(-1))
@@ -511,12 +493,12 @@ def test_dropped_entries_warn_through_the_sink():
     bad[3, 0] = -1
     bad[9, 1] = bad[9, 0]
     G.check_status()
-    _LL().apply(_dev(X), _dev(Y), 0.07, 1.0, k, neighbors=_dev(bad))
+    _LL().apply(A.dev(X), A.dev(Y), 0.07, 1.0, k, neighbors=A.dev(bad))
     with pytest.warns(UserWarning, match="2 list entries were dropped"):
         G.check_status()
     with warnings.catch_warnings():
         warnings.simplefilter("error")
-        _LL().apply(_dev(X), _dev(Y), 0.07, 1.0, k, neighbors=_dev(nbr))
+        _LL().apply(A.dev(X), A.dev(Y), 0.07, 1.0, k, neighbors=A.dev(nbr))
         G.check_status()
 
 
@@ -525,7 +507,7 @@ def test_dropped_entries_warn_through_the_sink():
 # ------------------------------------------------------------------------------------------------
 def test_argument_errors_on_the_device():
     X, Y, nbr, k = IR.layer_case("plumbing")
-    Xd, Yd = _dev(X), _dev(Y)
+    Xd, Yd = A.dev(X), A.dev(Y)
     n = X.shape[0]
     for bad in (torch.zeros(n, k + 1, dtype=torch.int64, device="cuda"),
                 torch.zeros(n, k - 2, dtype=torch.int64, device="cuda"),
@@ -542,4 +524,4 @@ def test_argument_errors_on_the_device():
         _G().device_graph(Xd, k, 1.0, neighbors=torch.zeros(n, k + 3, dtype=torch.int32))
     Xb = torch.stack([Xd, Xd])
     with pytest.raises(ValueError, match="neighbors"):
-        _LL().apply(Xb, Yd, 0.07, 1.0, k, neighbors=_dev(nbr))      # batched X needs B x n x (k-1)
+        _LL().apply(Xb, Yd, 0.07, 1.0, k, neighbors=A.dev(nbr))      # batched X needs B x n x (k-1)

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from oracle import gll_oracle as O
+from tests import abi as A
 from tests import ce_head_ref as R
 from tests import margin_ref as M
 from tests.margin_ref import LAYER_CASES, WELL_SEPARATED
@@ -36,18 +37,7 @@ def _gll():
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from graphlearninglayer_amd import _lib
-    _lib.lib()  # fail loudly when the HIP library is missing
-
-
-def _cuda(a):
-    return torch.from_numpy(np.array(a)).cuda()   # a copy: the shared inputs are read-only
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
+    A.need_gpu()
 
 
 def _layer(python=False):
@@ -63,7 +53,7 @@ def _loss_close(got, ref, row_margin):
     return abs(got - ref) <= (4 * m + 8) * U53 * float(np.mean(np.abs(row_margin)))
 
 
-def _same_bits(a, b):
+def _same_bits_nan_where_nan(a, b):
     """Bitwise equal float64 arrays, NaN where NaN."""
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     nan = np.isnan(b)
@@ -130,42 +120,38 @@ def _stage_call(lib, prob, B, ws, others, want_gbar, m, C):
     sec = torch.full((B, m), -7, dtype=torch.int64, device=dev)
     sb = lib.gll_margin_head_scratch_bytes(ct.byref(prob), B)
     scratch = torch.empty(max(sb, 1), dtype=torch.uint8, device=dev)
-    ot = _cuda(np.stack(others))
+    ot = A.dev(np.stack(others))
     _lib.check(lib.gll_margin_head_batched(
         ct.byref(prob), B, ws.data_ptr(), ot.data_ptr(), loss.data_ptr(),
         gbar.data_ptr() if want_gbar else None, row.data_ptr(), lab.data_ptr(), sec.data_ptr(),
         moved.data_ptr(), scratch.data_ptr() if sb else None,
         torch.cuda.current_stream().cuda_stream), "gll_margin_head")
     torch.cuda.synchronize()
-    return dict(loss=_np(loss), moved=_np(moved), gbar=_np(gbar) if want_gbar else None,
-                row=_np(row), labels=_np(lab), second=_np(sec), scratch_bytes=sb)
+    return dict(loss=A.host(loss), moved=A.host(moved), gbar=A.host(gbar) if want_gbar else None,
+                row=A.host(row), labels=A.host(lab), second=A.host(sec), scratch_bytes=sb)
 
 
 def _stage_workspace(m, C, graphs):
     """B workspace blocks of a small valid problem with the planted U32 rows of `graphs` written
     at P + base * C (gll_workspace_solve_view); no forward runs."""
     from graphlearninglayer_amd import _lib
-    lib = _lib.lib()
-    prob = _gll().make_problem(STAGE_BASE + m, STAGE_D, STAGE_BASE, C, STAGE_K, 0.07, 1.0)
-    nb = lib.gll_workspace_bytes(ct.byref(prob))
-    assert nb > 0
     B = len(graphs)
-    ws = torch.zeros(nb * B, dtype=torch.uint8, device="cuda")
+    # Run only for the problem and B zeroed blocks: its (zero) features and labels are never read
+    run = A.Run(np.zeros((B, STAGE_BASE + m, STAGE_D)), np.zeros((B, STAGE_BASE, C)), STAGE_K, 0.07,
+                1.0, ws_fill=0)
+    ws, nb = run.ws, run.wb
     for q, g in enumerate(graphs):
-        sv = _lib.SolveView()
-        _lib.check(lib.gll_workspace_solve_view(ct.byref(prob), ws.data_ptr() + q * nb,
-                                                ct.byref(sv)), "gll_workspace_solve_view")
-        off = sv.P - ws.data_ptr() + STAGE_BASE * C * 4
+        off = run.solve_view(q).P - ws.data_ptr() + STAGE_BASE * C * 4
         assert q * nb <= off and off + m * C * 4 <= (q + 1) * nb and off % 4 == 0
-        ws[off: off + m * C * 4].view(torch.float32).copy_(_cuda(_planted(m, C, g)[0]).reshape(-1))
-    return lib, prob, ws
+        ws[off: off + m * C * 4].view(torch.float32).copy_(A.dev(_planted(m, C, g)[0]).reshape(-1))
+    return _lib.lib(), run.problem(), ws
 
 
 def _check_stage(out, q, ref, m, C, tagline):
     np.testing.assert_array_equal(out["labels"][q], ref.labels, err_msg=tagline + " labels")
     np.testing.assert_array_equal(out["second"][q], ref.second, err_msg=tagline + " second")
     assert int(out["moved"][q]) == ref.moved, tagline
-    assert _same_bits(out["row"][q], ref.row_margin), tagline + " row_margin"
+    assert _same_bits_nan_where_nan(out["row"][q], ref.row_margin), tagline + " row_margin"
     if out["gbar"] is not None:
         g = out["gbar"][q]
         assert np.array_equal(g, ref.gbar), tagline + " gbar"
@@ -213,29 +199,28 @@ def test_stage_other_null_and_no_unlabeled_row():
                                            gbar.data_ptr(), row.data_ptr(), lab.data_ptr(),
                                            sec.data_ptr(), moved.data_ptr(), None, s),
                "gll_margin_head")
-    np.testing.assert_array_equal(_np(lab), ref.labels)
-    np.testing.assert_array_equal(_np(sec), ref.second)
+    np.testing.assert_array_equal(A.host(lab), ref.labels)
+    np.testing.assert_array_equal(A.host(sec), ref.second)
     assert float(loss) == 0.0 and int(moved) == 0
-    assert not _np(gbar).any() and not _np(row).any()
+    assert not A.host(gbar).any() and not A.host(row).any()
     # only loss given: every other output NULL
     loss.fill_(7.0)
-    ot = _cuda(_planted(m, C, 0)[1])
+    ot = A.dev(_planted(m, C, 0)[1])
     _lib.check(lib.gll_margin_head_batched(ct.byref(prob), 1, ws.data_ptr(), ot.data_ptr(),
                                            loss.data_ptr(), None, None, None, None, None, None, s),
                "gll_margin_head")
     full = _planted(m, C, 0)[2]
     assert _loss_close(float(loss), full.loss, full.row_margin)
     # m == 0: loss 0 and moved 0
-    p0 = _gll().make_problem(8, STAGE_D, 8, 3, STAGE_K, 0.07, 1.0)
-    nb = lib.gll_workspace_bytes(ct.byref(p0))
-    assert nb > 0
-    w0 = torch.zeros(nb * 2, dtype=torch.uint8, device="cuda")
+    # as above: only the problem and two zeroed blocks are used
+    empty = A.Run(np.zeros((2, 8, STAGE_D)), np.zeros((2, 8, 3)), STAGE_K, 0.07, 1.0, ws_fill=0)
+    p0, w0 = empty.problem(), empty.ws
     l0 = torch.full((2,), 7.0, dtype=torch.float64, device="cuda")
     m0 = torch.full((2,), -7, dtype=torch.int64, device="cuda")
     _lib.check(lib.gll_margin_head_batched(ct.byref(p0), 2, w0.data_ptr(), None, l0.data_ptr(),
                                            None, None, None, None, m0.data_ptr(), None, s),
                "gll_margin_head")
-    assert (_np(l0) == 0).all() and (_np(m0) == 0).all()
+    assert (A.host(l0) == 0).all() and (A.host(m0) == 0).all()
 
 
 # ------------------------------------------------------------------------------------------
@@ -256,9 +241,9 @@ def test_same_U_parity_with_pytorch(tag, eps, tau, python):
     X, Y, _ = R.inputs(tag)
     k = R.CASES[tag].k
     mg, apply = _layer(python)
-    Xt, Yt = _cuda(X), _cuda(Y)
+    Xt, Yt = A.dev(X), A.dev(Y)
     clean = mg(Xt, Yt, None, tau, eps, k)           # the attack's set-up step
-    assert float(clean[0]) == 0.0 and int(clean[5]) == 0 and not _np(clean[4]).any()
+    assert float(clean[0]) == 0.0 and int(clean[5]) == 0 and not A.host(clean[4]).any()
     other = clean[3]
     loss, pred, labels, second, row_margin, moved = mg(Xt, Yt, other, tau, eps, k)
     U = apply(Xt, Yt, tau, eps, k)
@@ -268,31 +253,31 @@ def test_same_U_parity_with_pytorch(tag, eps, tau, python):
     assert row_margin.shape == (m,) and row_margin.dtype == torch.float64
     assert moved.shape == () and moved.dtype == torch.int64
     assert not pred.requires_grad and loss.grad_fn is None
-    np.testing.assert_array_equal(_np(pred), _np(U))
-    np.testing.assert_array_equal(_np(clean[1]), _np(U))
-    np.testing.assert_array_equal(_np(clean[2]), _np(labels))
-    np.testing.assert_array_equal(_np(clean[3]), _np(second))
+    np.testing.assert_array_equal(A.host(pred), A.host(U))
+    np.testing.assert_array_equal(A.host(clean[1]), A.host(U))
+    np.testing.assert_array_equal(A.host(clean[2]), A.host(labels))
+    np.testing.assert_array_equal(A.host(clean[3]), A.host(second))
     idx = torch.arange(m, device=U.device)
-    t_row = _np(torch.clamp(U.max(1)[0] - U[idx, other], min=0))
+    t_row = A.host(torch.clamp(U.max(1)[0] - U[idx, other], min=0))
     t_loss = float(_gll().cw_margin(U, other))
-    ta, ts = (_np(v) for v in _torch_top2(U))
+    ta, ts = (A.host(v) for v in _torch_top2(U))
     print(f"{tag} eps={eps} tau={tau}: loss {float(loss):.17g} vs {t_loss:.17g} "
           f"(bound {(4 * m + 8) * U53 * np.mean(np.abs(t_row)):.2e}); moved {int(moved)} / {m}")
-    assert _same_bits(_np(row_margin), t_row)
+    assert _same_bits_nan_where_nan(A.host(row_margin), t_row)
     assert _loss_close(float(loss), t_loss, t_row)
-    Us = np.sort(_np(U), axis=1)
+    Us = np.sort(A.host(U), axis=1)
     tie1 = Us[:, -1] == Us[:, -2]
     tie2 = tie1 | (Us[:, -2] == Us[:, -3])
     assert tie2.sum() <= 0.01 * m
     if (tag, eps, tau) in WELL_SEPARATED:
         assert not tie2.any()
-    np.testing.assert_array_equal(_np(labels)[~tie1], ta[~tie1])
-    np.testing.assert_array_equal(_np(second)[~tie2], ts[~tie2])
-    assert int(moved) == int((_np(labels) == _np(other)).sum())
+    np.testing.assert_array_equal(A.host(labels)[~tie1], ta[~tie1])
+    np.testing.assert_array_equal(A.host(second)[~tie2], ts[~tie2])
+    assert int(moved) == int((A.host(labels) == A.host(other)).sum())
     # the yardstick on the same U
-    ref = M.margin_head(_np(U), _np(other))
-    np.testing.assert_array_equal(_np(labels), ref.labels)
-    np.testing.assert_array_equal(_np(second), ref.second)
+    ref = M.margin_head(A.host(U), A.host(other))
+    np.testing.assert_array_equal(A.host(labels), ref.labels)
+    np.testing.assert_array_equal(A.host(second), ref.second)
 
 
 # ------------------------------------------------------------------------------------------
@@ -309,7 +294,7 @@ def _clean(tag, eps, tau):
     """(labels, second) of a clean call, on the device."""
     X, Y, _ = R.inputs(tag)
     with torch.no_grad():
-        out = _gll().LaplaceLearningSparseHard.margin_loss(_cuda(X), _cuda(Y), None, tau, eps,
+        out = _gll().LaplaceLearningSparseHard.margin_loss(A.dev(X), A.dev(Y), None, tau, eps,
                                                            R.CASES[tag].k)
     return out[2], out[3]
 
@@ -319,12 +304,12 @@ def _grads(tag, eps, tau, fused, need=(True, False, False, False), python=False,
     X, Y, t = R.inputs(tag)
     k = R.CASES[tag].k
     mg, apply = _layer(python)
-    Xt = _cuda(X).requires_grad_(need[0])
-    Yt = _cuda(Y).requires_grad_(need[1])
+    Xt = A.dev(X).requires_grad_(need[0])
+    Yt = A.dev(Y).requires_grad_(need[1])
     tt, et = _scalar(tau, need[2]), _scalar(eps, need[3])
     other = _clean(tag, eps, tau)[1] if other is None else other
     if head == "ce":
-        loss = _gll().LaplaceLearningSparseHard.ce_loss(Xt, Yt, _cuda(t), tt, et, k)[0]
+        loss = _gll().LaplaceLearningSparseHard.ce_loss(Xt, Yt, A.dev(t), tt, et, k)[0]
     elif fused:
         loss = mg(Xt, Yt, other, tt, et, k)[0]
     else:
@@ -333,7 +318,7 @@ def _grads(tag, eps, tau, fused, need=(True, False, False, False), python=False,
     torch.cuda.synchronize()
 
     def g(v):
-        return None if not torch.is_tensor(v) or v.grad is None else _np(v.grad)
+        return None if not torch.is_tensor(v) or v.grad is None else A.host(v.grad)
     return dict(loss=float(loss.detach()), X=g(Xt), Y=g(Yt), tau=g(tt), eps=g(et))
 
 
@@ -368,12 +353,12 @@ def test_parameter_gradients_match_the_unfused_route():
 def test_other_equal_to_labels_gives_an_exactly_zero_gradient():
     labels = _clean("T1", 1.0, 0.07)[0]
     X, Y, _ = R.inputs("T1")
-    Xt = _cuda(X).requires_grad_(True)
-    out = _gll().LaplaceLearningSparseHard.margin_loss(Xt, _cuda(Y), labels, 0.07, 1.0,
+    Xt = A.dev(X).requires_grad_(True)
+    out = _gll().LaplaceLearningSparseHard.margin_loss(Xt, A.dev(Y), labels, 0.07, 1.0,
                                                        R.CASES["T1"].k)
-    assert float(out[0].detach()) == 0.0 and not _np(out[4]).any() and int(out[5]) == len(labels)
+    assert float(out[0].detach()) == 0.0 and not A.host(out[4]).any() and int(out[5]) == len(labels)
     out[0].backward()
-    assert Xt.grad is not None and not _np(Xt.grad).any()
+    assert Xt.grad is not None and not A.host(Xt.grad).any()
 
 
 # ------------------------------------------------------------------------------------------
@@ -387,31 +372,25 @@ def test_launch_accounting():
     def counts(tag, eps, tau, **kw):
         out = {}
         for kid in kids:   # one kernel id at a time: a bracket pair is armed per thread
-            _lib.prof_enable(kid, 1)
-            _grads(tag, eps, tau, **kw)
-            out[kid] = _lib.prof_read(kid)[1]
-            _lib.prof_enable(kid, 0)
+            with A.launches(kid) as ran:
+                _grads(tag, eps, tau, **kw)
+            out[kid] = ran[0]
         return out
 
-    try:
-        # T1 / T2: adjoint CG + gradient launches (fixed / auto eps); NS: the fused backward
-        for tag, eps, tau in (("T1", 1.0, 0.07), ("T2", "auto", 0.0), R.NS):
-            _grads(tag, eps, tau, True)   # warm (and the cached clean call)
-            a = counts(tag, eps, tau, fused=True)
-            b = counts(tag, eps, tau, fused=False)
-            c = counts(tag, eps, tau, fused=True, head="ce")
-            print(f"{tag}: launches margin_loss {a}, apply {b}, ce_loss {c}")
-            assert a[_lib.K_LOSS] == 1 and b[_lib.K_LOSS] == 0
-            for kid in kids[:-1]:
-                assert a[kid] == b[kid], _lib.kernel_name(kid)
-            assert a == c                 # forward and backward launch what ce_loss's do
-            assert sum(a[kid] for kid in kids[:-1]) >= 5
-            if tag == "NS":
-                assert a[_lib.K_BWD] == 1   # the saved gbar still takes the one-launch backward
-    finally:
-        for kid in kids:
-            _lib.prof_enable(kid, 0)
-            _lib.prof_read(kid)
+    # T1 / T2: adjoint CG + gradient launches (fixed / auto eps); NS: the fused backward
+    for tag, eps, tau in (("T1", 1.0, 0.07), ("T2", "auto", 0.0), R.NS):
+        _grads(tag, eps, tau, True)   # warm (and the cached clean call)
+        a = counts(tag, eps, tau, fused=True)
+        b = counts(tag, eps, tau, fused=False)
+        c = counts(tag, eps, tau, fused=True, head="ce")
+        print(f"{tag}: launches margin_loss {a}, apply {b}, ce_loss {c}")
+        assert a[_lib.K_LOSS] == 1 and b[_lib.K_LOSS] == 0
+        for kid in kids[:-1]:
+            assert a[kid] == b[kid], _lib.kernel_name(kid)
+        assert a == c                 # forward and backward launch what ce_loss's do
+        assert sum(a[kid] for kid in kids[:-1]) >= 5
+        if tag == "NS":
+            assert a[_lib.K_BWD] == 1   # the saved gbar still takes the one-launch backward
 
 
 # ------------------------------------------------------------------------------------------
@@ -423,26 +402,26 @@ def test_no_grad_and_consumed_graph(python):
     k = R.CASES["T1"].k
     mg, _ = _layer(python)
     other = _clean("T1", 1.0, 0.07)[1]
-    Xt = _cuda(X).requires_grad_(True)
-    full = mg(Xt, _cuda(Y), other, 0.07, 1.0, k)
+    Xt = A.dev(X).requires_grad_(True)
+    full = mg(Xt, A.dev(Y), other, 0.07, 1.0, k)
     assert len(full) == 6
     assert full[0].requires_grad and not any(o.requires_grad for o in full[1:])
     with torch.no_grad():
-        ng = mg(Xt, _cuda(Y), other, 0.07, 1.0, k)
-    plain = mg(_cuda(X), _cuda(Y), other, 0.07, 1.0, k)   # no input requires grad
+        ng = mg(Xt, A.dev(Y), other, 0.07, 1.0, k)
+    plain = mg(A.dev(X), A.dev(Y), other, 0.07, 1.0, k)   # no input requires grad
     for outs in (ng, plain):
         assert not outs[0].requires_grad and outs[0].grad_fn is None
         for a, b in zip(outs, full):
-            np.testing.assert_array_equal(_np(a), _np(b))
+            np.testing.assert_array_equal(A.host(a), A.host(b))
     full[0].backward()
     with pytest.raises(RuntimeError):
         full[0].backward()
     # argument handling: shape and dtype of other
     with pytest.raises(ValueError):
-        mg(_cuda(X), _cuda(Y), other[:-1], 0.07, 1.0, k)
+        mg(A.dev(X), A.dev(Y), other[:-1], 0.07, 1.0, k)
     with pytest.raises(TypeError):
-        mg(_cuda(X), _cuda(Y), other.float(), 0.07, 1.0, k)
-    i32 = mg(_cuda(X), _cuda(Y), other.int(), 0.07, 1.0, k)
+        mg(A.dev(X), A.dev(Y), other.float(), 0.07, 1.0, k)
+    i32 = mg(A.dev(X), A.dev(Y), other.int(), 0.07, 1.0, k)
     assert float(i32[0]) == float(full[0])
     # CPU input: every output comes back on the CPU, the gradient too
     Xc = torch.from_numpy(np.array(X)).requires_grad_(True)
@@ -450,7 +429,7 @@ def test_no_grad_and_consumed_graph(python):
     assert all(o.device.type == "cpu" for o in outs)
     outs[0].backward()
     assert Xc.grad.device.type == "cpu" and float(outs[0]) == float(full[0])
-    np.testing.assert_array_equal(Xc.grad.numpy(), _np(Xt.grad))
+    np.testing.assert_array_equal(Xc.grad.numpy(), A.host(Xt.grad))
 
 
 def test_batched_graphs_equal_single_calls():
@@ -459,17 +438,17 @@ def test_batched_graphs_equal_single_calls():
     Ys = np.stack([R.inputs(g)[1] for g in tags])
     L = _gll().LaplaceLearningSparseHard
     with torch.no_grad():
-        clean = L.margin_loss(_cuda(Xs), _cuda(Ys), None, tau, eps, k)
+        clean = L.margin_loss(A.dev(Xs), A.dev(Ys), None, tau, eps, k)
     other = clean[3]
     assert other.shape == (3, Xs.shape[1] - Ys.shape[1])
-    outb = L.margin_loss(_cuda(Xs), _cuda(Ys), other, tau, eps, k)
+    outb = L.margin_loss(A.dev(Xs), A.dev(Ys), other, tau, eps, k)
     assert outb[0].shape == (3,) and outb[5].shape == (3,) and outb[4].shape == other.shape
     for g in range(3):
-        out1 = L.margin_loss(_cuda(Xs[g]), _cuda(Ys[g]), other[g], tau, eps, k)
+        out1 = L.margin_loss(A.dev(Xs[g]), A.dev(Ys[g]), other[g], tau, eps, k)
         for a, b in zip(out1, outb):
-            np.testing.assert_array_equal(_np(a), _np(b[g]))
+            np.testing.assert_array_equal(A.host(a), A.host(b[g]))
     with pytest.raises(ValueError):
-        L.margin_loss(_cuda(Xs), _cuda(Ys), other[0], tau, eps, k)
+        L.margin_loss(A.dev(Xs), A.dev(Ys), other[0], tau, eps, k)
 
 
 def test_three_step_cw_adam_loop():
@@ -481,7 +460,7 @@ def test_three_step_cw_adam_loop():
     L = _gll().LaplaceLearningSparseHard
 
     def attack(fused):
-        Xt, Yt = _cuda(X), _cuda(Y)
+        Xt, Yt = A.dev(X), A.dev(Y)
         base_data, data = Xt[:c.base], Xt[c.base:]
         with torch.no_grad():
             if fused:
@@ -503,7 +482,7 @@ def test_three_step_cw_adam_loop():
             loss.backward()
             opt.step()
             losses.append(float(loss.detach()))
-        return _np(w), losses, _np(next_pred)
+        return A.host(w), losses, A.host(next_pred)
 
     wa, la, na = attack(True)
     wb, lb, nb = attack(False)

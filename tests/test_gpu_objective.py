@@ -23,6 +23,7 @@ import pytest
 import torch
 
 from oracle import gll_oracle as O
+from tests import abi as A
 from tests import ce_head_ref as R
 from tests import grad_ref
 from tests import objective_ref as OB
@@ -42,18 +43,7 @@ def _gll():
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from graphlearninglayer_amd import _lib
-    _lib.lib()  # fail loudly when the HIP library is missing
-
-
-def _cuda(a):
-    return torch.from_numpy(np.array(a)).cuda()   # a copy: the shared inputs are read-only
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
+    A.need_gpu()
 
 
 def _layer(python=False):
@@ -78,17 +68,6 @@ def _loss_bound(ref, m):
     return (4 * m + 8) * U53 * float(np.mean(ref.row_abs[fin])) if fin.any() else 0.0
 
 
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def _same_bits(a, b, msg=""):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.dtype == b.dtype and a.shape == b.shape, msg
-    np.testing.assert_array_equal(_bits(a), _bits(b), err_msg=msg)
-
-
 # ------------------------------------------------------------------------------------------
 # 1. same-U parity with the float64 reference
 # ------------------------------------------------------------------------------------------
@@ -99,10 +78,10 @@ def test_same_U_parity_with_the_reference(tag, eps, tau, weights, python):
     X, Y, t = R.inputs(tag)
     k = R.CASES[tag].k
     objective, _, apply = _layer(python)
-    Xt, Yt, tt = _cuda(X), _cuda(Y), _cuda(t)
+    Xt, Yt, tt = A.dev(X), A.dev(Y), A.dev(t)
     loss, pred, labels, row_loss, correct, row_ent, row_l2 = objective(Xt, Yt, tt, tau, eps, k,
                                                                        weights=weights)
-    U = _np(apply(Xt, Yt, tau, eps, k))
+    U = A.host(apply(Xt, Yt, tau, eps, k))
     m, C = U.shape
     assert loss.shape == () and loss.dtype == torch.float64 and loss.is_cuda
     assert pred.dtype == torch.float64 and labels.dtype == torch.int64
@@ -110,9 +89,9 @@ def test_same_U_parity_with_the_reference(tag, eps, tau, weights, python):
         assert r.shape == (m,) and r.dtype == torch.float64
     assert correct.shape == () and correct.dtype == torch.int64
     assert not pred.requires_grad and loss.grad_fn is None
-    np.testing.assert_array_equal(_np(pred), U)
+    np.testing.assert_array_equal(A.host(pred), U)
     ref = OB.objective(U, t, weights)
-    a_row, a_ent, a_l2, a_loss = _np(row_loss), _np(row_ent), _np(row_l2), float(loss)
+    a_row, a_ent, a_l2, a_loss = A.host(row_loss), A.host(row_ent), A.host(row_l2), float(loss)
     b_row = 8 * U53 * np.maximum(np.abs(ref.row_ce), 1.0)
     b_ent = 8 * (C + 1) * U53 * np.maximum(1.0, ref.ent_abs)
     b_l2 = (C + 4) * U53 * np.maximum(1.0, ref.sq)
@@ -133,10 +112,10 @@ def test_same_U_parity_with_the_reference(tag, eps, tau, weights, python):
     assert _close(a_ent, ref.row_entropy, b_ent)
     assert _close(a_l2, ref.row_l2, b_l2)
     assert _close(a_loss, ref.loss, b_loss)
-    assert int(correct) == int((_np(labels) == t).sum())
+    assert int(correct) == int((A.host(labels) == t).sum())
     Us = np.sort(U, axis=1)
     tie = Us[:, -1] == Us[:, -2]
-    np.testing.assert_array_equal(_np(labels)[~tie], ref.pred_label[~tie])
+    np.testing.assert_array_equal(A.host(labels)[~tie], ref.pred_label[~tie])
 
 
 # ------------------------------------------------------------------------------------------
@@ -147,20 +126,15 @@ def _abi_head(tag, eps, tau, weights, targets="own", want_gbar=True, score=0, sc
     """gll_forward + gll_objective_head_batched over ctypes; every output as numpy.  targets:
     'own' (the case's), None (NULL) or an array."""
     from graphlearninglayer_amd import _lib
-    GLL = _gll()
     X, Y, t = R.inputs(tag)
     t = t if isinstance(targets, str) else targets
     c = R.CASES[tag]
-    n, m = c.base + c.batch, c.batch
+    m = c.batch
     lib = _lib.lib()
-    prob = GLL.make_problem(n, c.d, c.base, c.C, c.k, tau, eps)
-    ws = torch.empty(lib.gll_workspace_bytes(ct.byref(prob)), dtype=torch.uint8, device="cuda")
-    Xt, Yt = _cuda(X), _cuda(Y)
-    tt = None if t is None else _cuda(np.asarray(t, dtype=np.int64))
-    U = torch.empty(m, c.C, dtype=torch.float64, device="cuda")
-    s = torch.cuda.current_stream().cuda_stream
-    _lib.check(lib.gll_forward(ct.byref(prob), Xt.data_ptr(), Yt.data_ptr(), _lib.GLL_DT_F32,
-                               ws.data_ptr(), U.data_ptr(), s), "gll_forward")
+    run = A.Run(X, Y, c.k, tau, eps)
+    prob, ws, s = run.problem(), run.ws, A.stream()
+    tt = None if t is None else A.dev(np.asarray(t, dtype=np.int64))
+    U = run.forward()
     f64 = dict(dtype=torch.float64, device="cuda")
     loss = torch.empty(1, **f64)
     gbar = torch.full((m, c.C), 7.0, dtype=torch.float32, device="cuda") if want_gbar else None
@@ -168,7 +142,7 @@ def _abi_head(tag, eps, tau, weights, targets="own", want_gbar=True, score=0, sc
     lab = torch.empty(m, dtype=torch.int64, device="cuda")
     cor = torch.empty(1, dtype=torch.int64, device="cuda")
     store = torch.full((max(score_len, 1),), sentinel, dtype=torch.float32, device="cuda")
-    ind = None if indices is None else _cuda(np.asarray(indices, dtype=np.int64))
+    ind = None if indices is None else A.dev(np.asarray(indices, dtype=np.int64))
     sb = lib.gll_objective_head_scratch_bytes(ct.byref(prob), 1)
     scratch = torch.empty(max(sb, 1), dtype=torch.uint8, device="cuda")
     _lib.check(lib.gll_objective_head_batched(
@@ -178,8 +152,8 @@ def _abi_head(tag, eps, tau, weights, targets="own", want_gbar=True, score=0, sc
         store.data_ptr() if score else None, score_len, None if ind is None else ind.data_ptr(),
         scratch.data_ptr() if sb else None, s), "gll_objective_head")
     torch.cuda.synchronize()
-    return dict(U=_np(U), loss=_np(loss)[0], gbar=_np(gbar) if want_gbar else None, row=_np(row),
-                ent=_np(ent), l2=_np(l2), labels=_np(lab), correct=int(cor), store=_np(store))
+    return dict(U=U, loss=A.host(loss)[0], gbar=A.host(gbar) if want_gbar else None, row=A.host(row),
+                ent=A.host(ent), l2=A.host(l2), labels=A.host(lab), correct=int(cor), store=A.host(store))
 
 
 def _check_gbar(out, ref, label):
@@ -209,7 +183,7 @@ def test_gbar_through_the_c_abi(tag, eps, tau, weights):
     # without gbar the other outputs do not move
     bare = _abi_head(tag, eps, tau, weights, want_gbar=False)
     for key in ("loss", "row", "ent", "l2"):
-        _same_bits(bare[key], out[key], key)
+        A.same_bits(bare[key], out[key], key)
     for key in ("labels", "correct"):
         np.testing.assert_array_equal(bare[key], out[key], err_msg=key)
 
@@ -230,10 +204,10 @@ def test_masked_and_absent_targets(tag, eps, tau):
     part = _abi_head(tag, eps, tau, w, targets=tm)
     ref = OB.objective(part["U"], tm, w)
     assert (part["row"][masked] == 0).all()
-    _same_bits(part["row"][~masked], full["row"][~masked])
-    _same_bits(part["ent"], full["ent"])           # the regularisers see every row
-    _same_bits(part["l2"], full["l2"])
-    _same_bits(part["gbar"][~masked], full["gbar"][~masked])
+    A.same_bits(part["row"][~masked], full["row"][~masked])
+    A.same_bits(part["ent"], full["ent"])           # the regularisers see every row
+    A.same_bits(part["l2"], full["l2"])
+    A.same_bits(part["gbar"][~masked], full["gbar"][~masked])
     np.testing.assert_array_equal(part["labels"], full["labels"])
     assert part["correct"] == ref.correct == int((part["labels"][~masked] == t[~masked]).sum())
     _check_gbar(part, ref, f"{tag} partly masked")
@@ -243,7 +217,7 @@ def test_masked_and_absent_targets(tag, eps, tau):
     null = _abi_head(tag, eps, tau, w, targets=None)
     ref0 = OB.objective(allm["U"], None, w)
     for key in ("loss", "row", "ent", "l2", "gbar"):
-        _same_bits(allm[key], null[key], key)
+        A.same_bits(allm[key], null[key], key)
     np.testing.assert_array_equal(allm["labels"], null["labels"])
     assert allm["correct"] == null["correct"] == 0 and (null["row"] == 0).all()
     _check_gbar(null, ref0, f"{tag} targets NULL")
@@ -270,9 +244,9 @@ def _step(tag, eps, tau, head, need=(True, False, False, False), python=False, w
     X, Y, t = R.inputs(tag)
     k = R.CASES[tag].k
     objective, ce, apply = _layer(python)
-    Xt = _cuda(X).requires_grad_(need[0])
-    Yt = _cuda(Y).requires_grad_(need[1])
-    tt, et, tg = _scalar(tau, need[2]), _scalar(eps, need[3]), _cuda(t)
+    Xt = A.dev(X).requires_grad_(need[0])
+    Yt = A.dev(Y).requires_grad_(need[1])
+    tt, et, tg = _scalar(tau, need[2]), _scalar(eps, need[3]), A.dev(t)
     w = (1.0, 0.0, 0.0) if weights is None else weights
     outs = ()
     if head == "objective":
@@ -303,9 +277,9 @@ def _step(tag, eps, tau, head, need=(True, False, False, False), python=False, w
     torch.cuda.synchronize()
 
     def g(v):
-        return None if not torch.is_tensor(v) or v.grad is None else _np(v.grad)
-    return dict(loss=_np(loss), X=g(Xt), Y=g(Yt), tau=g(tt), eps=g(et),
-                outs=[_np(o) for o in outs], launches=launches)
+        return None if not torch.is_tensor(v) or v.grad is None else A.host(v.grad)
+    return dict(loss=A.host(loss), X=g(Xt), Y=g(Yt), tau=g(tt), eps=g(et),
+                outs=[A.host(o) for o in outs], launches=launches)
 
 
 @pytest.mark.parametrize("python", [False, True], ids=["native", "ctypes"])
@@ -317,17 +291,17 @@ def test_unit_ce_weight_is_the_ce_head_bitwise(tag, eps, tau, python):
     b = _step(tag, eps, tau, "ce", need, python)
     assert len(a["outs"]) == 7 and len(b["outs"]) == 5
     for q, name in enumerate(("loss", "pred", "pred_labels", "row_loss", "correct")):
-        _same_bits(a["outs"][q], b["outs"][q], name)
+        A.same_bits(a["outs"][q], b["outs"][q], name)
     for key in ("X", "Y", "tau", "eps"):
         if b[key] is None:
             assert a[key] is None, key
         else:
-            _same_bits(a[key], b[key], "grad " + key)
+            A.same_bits(a[key], b[key], "grad " + key)
     assert a["X"] is not None and a["Y"] is not None and a["tau"] is not None
     # explicit weights (1, 0, 0) and integers are the default
     c = _step(tag, eps, tau, "objective", need, python, weights=(1, 0, 0))
-    _same_bits(c["loss"], a["loss"])
-    _same_bits(c["X"], a["X"])
+    A.same_bits(c["loss"], a["loss"])
+    A.same_bits(c["X"], a["X"])
 
 
 # ------------------------------------------------------------------------------------------
@@ -360,7 +334,7 @@ def test_parameter_gradients_match_the_unfused_route():
         assert v < TOL, key
     p = _step("T1", 1.0, 0.07, "objective", need, python=True, weights=w)
     for key in ("loss", "X", "Y", "tau", "eps"):
-        _same_bits(a[key], p[key], key)
+        A.same_bits(a[key], p[key], key)
 
 
 # ------------------------------------------------------------------------------------------
@@ -393,20 +367,20 @@ def test_scatter(tag, N, score, python):
     C = R.CASES[tag].C
     objective = _layer(python)[0]
     store = torch.full((N,), SENTINEL, dtype=torch.float32, device="cuda")
-    outs = objective(_cuda(X), _cuda(Y), _cuda(tm), tau, eps, k, weights=(1.0, 0.3, 0.1),
-                     score=score, score_out=store, indices=_cuda(ind))
-    row = _np(outs[3] if score == "entropy" else outs[6]).astype(np.float32)
-    got = _np(store)
+    outs = objective(A.dev(X), A.dev(Y), A.dev(tm), tau, eps, k, weights=(1.0, 0.3, 0.1),
+                     score=score, score_out=store, indices=A.dev(ind))
+    row = A.host(outs[3] if score == "entropy" else outs[6]).astype(np.float32)
+    got = A.host(store)
     live = (tm >= 0) & (tm < C) & (ind >= 0) & (ind < N)
     assert 0 < live.sum() < len(tm) - 4
     want = np.full(N, SENTINEL, dtype=np.float32)
     want[ind[live]] = row[live]
-    _same_bits(got, want)                       # written rows bitwise, every other entry untouched
+    A.same_bits(got, want)                       # written rows bitwise, every other entry untouched
     assert (got[ind[live]] != SENTINEL).all()
     # the outputs do not depend on the scatter
-    plain = objective(_cuda(X), _cuda(Y), _cuda(tm), tau, eps, k, weights=(1.0, 0.3, 0.1))
+    plain = objective(A.dev(X), A.dev(Y), A.dev(tm), tau, eps, k, weights=(1.0, 0.3, 0.1))
     for a, b in zip(outs, plain):
-        _same_bits(_np(a), _np(b))
+        A.same_bits(A.host(a), A.host(b))
 
 
 @pytest.mark.parametrize("score", ["entropy", "l2"])
@@ -416,14 +390,14 @@ def test_scatter_with_duplicate_indices_stores_one_candidate(score):
     ind = np.arange(m, dtype=np.int64) % 8 + 3            # 8 slots, 8 candidates each
     store = torch.full((N,), SENTINEL, dtype=torch.float32, device="cuda")
     L = _gll().LaplaceLearningSparseHard
-    outs = L.objective(_cuda(X), _cuda(Y), _cuda(t), 0.07, 1.0, R.CASES["T1"].k, score=score,
-                       score_out=store, indices=_cuda(ind))
-    row = _np(outs[3] if score == "entropy" else outs[6]).astype(np.float32)
-    got = _np(store)
+    outs = L.objective(A.dev(X), A.dev(Y), A.dev(t), 0.07, 1.0, R.CASES["T1"].k, score=score,
+                       score_out=store, indices=A.dev(ind))
+    row = A.host(outs[3] if score == "entropy" else outs[6]).astype(np.float32)
+    got = A.host(store)
     for slot in range(N):
         cands = row[ind == slot]
         if cands.size:
-            assert (_bits(cands) == _bits(got[slot:slot + 1])[0]).any(), slot
+            assert (A.bits(cands) == A.bits(got[slot:slot + 1])[0]).any(), slot
         else:
             assert got[slot] == SENTINEL
 
@@ -432,7 +406,7 @@ def test_scatter_argument_checks():
     X, Y, t = R.inputs("T1")
     L = _gll().LaplaceLearningSparseHard
     k = R.CASES["T1"].k
-    Xt, Yt, tt = _cuda(X), _cuda(Y), _cuda(t)
+    Xt, Yt, tt = A.dev(X), A.dev(Y), A.dev(t)
     ind = torch.arange(len(t), device="cuda")
     good = torch.zeros(100, device="cuda")
     for fn in (L.objective, L.objective_python):
@@ -461,7 +435,7 @@ def test_scatter_argument_checks():
     assert all(o.device.type == "cpu" for o in outs)
     outs[0].backward()
     assert Xc.grad.device.type == "cpu"
-    _same_bits(_np(good[:len(t)]), outs[6].numpy().astype(np.float32))
+    A.same_bits(A.host(good[:len(t)]), outs[6].numpy().astype(np.float32))
 
 
 # ------------------------------------------------------------------------------------------
@@ -479,58 +453,58 @@ def test_batched_graphs_equal_single_calls(shared):
     ind = np.random.default_rng(1).permutation(N)[:3 * m].reshape(3, m).astype(np.int64)
     ind[2, 7] = N
     L = _gll().LaplaceLearningSparseHard
-    Yb = _cuda(Ys[0]) if shared else _cuda(Ys)
+    Yb = A.dev(Ys[0]) if shared else A.dev(Ys)
     store = torch.full((N,), SENTINEL, dtype=torch.float32, device="cuda")
-    Xb = _cuda(Xs).requires_grad_(True)
-    outb = L.objective(Xb, Yb, _cuda(ts), tau, eps, k, weights=w, score="l2", score_out=store,
-                       indices=_cuda(ind))
+    Xb = A.dev(Xs).requires_grad_(True)
+    outb = L.objective(Xb, Yb, A.dev(ts), tau, eps, k, weights=w, score="l2", score_out=store,
+                       indices=A.dev(ind))
     assert outb[0].shape == (3,) and outb[4].shape == (3,) and outb[1].shape == (3, m, Ys.shape[2])
     for q in (2, 3, 5, 6):
         assert outb[q].shape == (3, m)
     outb[0].sum().backward()
-    gb = _np(Xb.grad)
-    Xa = _cuda(Xs).requires_grad_(True)          # apply's own batched backward: bitwise the single?
+    gb = A.host(Xb.grad)
+    Xa = A.dev(Xs).requires_grad_(True)          # apply's own batched backward: bitwise the single?
     Ua = L.apply(Xa, Yb, tau, eps, k)
     Ua.backward(torch.ones_like(Ua))
     single_store = torch.full((N,), SENTINEL, dtype=torch.float32, device="cuda")
     for g in range(3):
-        X1 = _cuda(Xs[g]).requires_grad_(True)
-        out1 = L.objective(X1, _cuda(Ys[g]), _cuda(ts[g]), tau, eps, k, weights=w, score="l2",
-                           score_out=single_store, indices=_cuda(ind[g]))
+        X1 = A.dev(Xs[g]).requires_grad_(True)
+        out1 = L.objective(X1, A.dev(Ys[g]), A.dev(ts[g]), tau, eps, k, weights=w, score="l2",
+                           score_out=single_store, indices=A.dev(ind[g]))
         out1[0].backward()
         for q, (a, b) in enumerate(zip(out1, outb)):
-            _same_bits(_np(a), _np(b[g]), f"graph {g} output {q}")
-        Xs1 = _cuda(Xs[g]).requires_grad_(True)
-        U1 = L.apply(Xs1, _cuda(Ys[g]), tau, eps, k)
+            A.same_bits(A.host(a), A.host(b[g]), f"graph {g} output {q}")
+        Xs1 = A.dev(Xs[g]).requires_grad_(True)
+        U1 = L.apply(Xs1, A.dev(Ys[g]), tau, eps, k)
         U1.backward(torch.ones_like(U1))
-        apply_bitwise = np.array_equal(_np(Xa.grad[g]), _np(Xs1.grad))
-        e = O.rel_err(gb[g], _np(X1.grad))
+        apply_bitwise = np.array_equal(A.host(Xa.grad[g]), A.host(Xs1.grad))
+        e = O.rel_err(gb[g], A.host(X1.grad))
         print(f"graph {g}: apply batched == single bitwise: {apply_bitwise}; "
               f"objective batched vs single grad_X rel err {e:.2e}")
         if apply_bitwise:
-            np.testing.assert_array_equal(gb[g], _np(X1.grad))
+            np.testing.assert_array_equal(gb[g], A.host(X1.grad))
         else:   # other kernel variants in the batched launch: test_gpu_parity's bar for them
             assert e <= 1e-5
         # this graph's loss alone: the others get an exact-zero gradient
-        Xc = _cuda(Xs).requires_grad_(True)
-        L.objective(Xc, Yb, _cuda(ts), tau, eps, k, weights=w)[0][g].backward()
-        gc = _np(Xc.grad)
+        Xc = A.dev(Xs).requires_grad_(True)
+        L.objective(Xc, Yb, A.dev(ts), tau, eps, k, weights=w)[0][g].backward()
+        gc = A.host(Xc.grad)
         for other in range(3):
             if other != g:
                 assert (gc[other] == 0).all()
         np.testing.assert_array_equal(gc[g], gb[g])
     # one store took all B x m indices: the same entries as the three single calls
-    _same_bits(_np(store), _np(single_store))
+    A.same_bits(A.host(store), A.host(single_store))
     live = (ts >= 0) & (ind < N)
-    assert (_np(store)[ind[live]] != SENTINEL).all()
-    assert int((_np(store) != SENTINEL).sum()) == int(live.sum())
+    assert (A.host(store)[ind[live]] != SENTINEL).all()
+    assert int((A.host(store) != SENTINEL).sum()) == int(live.sum())
     # the ctypes path runs the same kernels on the same numbers
     pstore = torch.full((N,), SENTINEL, dtype=torch.float32, device="cuda")
-    outp = L.objective_python(_cuda(Xs), Yb, _cuda(ts), tau, eps, k, weights=w, score="l2",
-                              score_out=pstore, indices=_cuda(ind))
+    outp = L.objective_python(A.dev(Xs), Yb, A.dev(ts), tau, eps, k, weights=w, score="l2",
+                              score_out=pstore, indices=A.dev(ind))
     for a, b in zip(outp, outb):
-        _same_bits(_np(a), _np(b))
-    _same_bits(_np(pstore), _np(store))
+        A.same_bits(A.host(a), A.host(b))
+    A.same_bits(A.host(pstore), A.host(store))
 
 
 # ------------------------------------------------------------------------------------------
@@ -540,14 +514,10 @@ def test_launch_counts():
     from graphlearninglayer_amd import _lib
 
     def launches(head, tag, eps, tau):
-        _lib.prof_read(_lib.K_LOSS)
-        _lib.prof_enable(_lib.K_LOSS, 1)
-        try:
+        with A.launches(_lib.K_LOSS) as ran:
             got = _step(tag, eps, tau, head, weights=(1.0, 0.3, 0.1) if head != "ce" else None,
                         count=True)["launches"]
-            return got, _lib.prof_read(_lib.K_LOSS)[1]
-        finally:
-            _lib.prof_enable(_lib.K_LOSS, 0)
+        return got, ran[0]
 
     for tag, eps, tau in (("T1", 1.0, 0.07), ("T2", "auto", 0.0), R.NS):
         c = R.CASES[tag]
@@ -603,7 +573,7 @@ def test_fullysup_shaped_steps_with_the_score_store():
             score_out=store.scores, indices=idx)
         loss.backward()
         assert feats.grad is not None and bool(torch.isfinite(feats.grad).all())
-        _same_bits(_np(store.scores[idx]), _np(row_l2).astype(np.float32))
+        A.same_bits(A.host(store.scores[idx]), A.host(row_l2).astype(np.float32))
         want = (1.0 - torch.sum(pred ** 2, 1)).float()      # FullySup.py:171 on the same pred
         assert float((store.scores[idx] - want).abs().max()) <= 2.0 ** -23
     host = store.scores.cpu()                               # two steps covered the training set

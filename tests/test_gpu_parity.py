@@ -15,39 +15,20 @@ import numpy as np
 import pytest
 import torch
 
+from graphlearninglayer_amd import GLL
 from oracle import gll_oracle as O
+from tests import abi as A
 from tests.golden_io import Case, nan_aware, names
+from tests.parity_runs import (TOL, batched_knn_lists, exact_knn_rows, forward_c_abi,
+                                fwd_bwd_batched_c_abi, fwd_bwd_c_abi, gpu_knn, run_layer,
+                                synth_batch)
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-4
-
-
-def _gll():
-    from graphlearninglayer_amd import GLL
-    return GLL
-
-
-def _run(X, Y, tau, eps, k, gbar, dev="cuda"):
-    GLL = _gll()
-    Xt = torch.from_numpy(np.ascontiguousarray(X)).to(dev).requires_grad_(True)
-    Yt = torch.from_numpy(np.ascontiguousarray(Y)).to(dev)
-    U = GLL.LaplaceLearningSparseHard.apply(Xt, Yt, tau, eps, k)
-    U.backward(torch.from_numpy(gbar).to(U.device))
-    torch.cuda.synchronize()
-    return U.detach().cpu().numpy(), Xt.grad.detach().cpu().numpy()
-
-
-def _gpu_knn(X, k, eps="auto"):
-    g = _gll().device_graph(torch.from_numpy(np.ascontiguousarray(X)).cuda(), k, eps)
-    return g
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from graphlearninglayer_amd import _lib
-    _lib.lib()  # fail loudly when the HIP library is missing
+    A.need_gpu()
 
 
 @pytest.mark.parametrize("name", names())
@@ -55,10 +36,10 @@ def test_parity_against_reference_fixture(name):
     c = Case(name)
     assert c.x_ok
     Y = c.Y if c.meta["ydtype"] == "f32" else c.Y.astype(np.int64)
-    U, grad = _run(c.X, Y, c.tau, c.eps, c.k, c.gbar)
+    U, grad = run_layer(c.X, Y, c.tau, c.eps, c.k, c.gbar)
     assert U.dtype == np.float64 and U.shape == c.U.shape
     # graph-level parity with the GPU's own kNN
-    g = _gpu_knn(c.X, c.k)
+    g = gpu_knn(c.X, c.k)
     ind = g["knn_idx"].cpu().numpy().astype(np.int64)
     with np.errstate(divide="ignore", invalid="ignore"):   # eps = 0 divides by zero
         Uo, st = O.forward(c.X, c.Y, c.tau, c.eps, c.k, knn=(ind, None))
@@ -80,7 +61,7 @@ def test_parity_against_reference_fixture(name):
 
 def test_knn_lists_ordered_and_self_first():
     c = Case("ns_eps1p0_tau0p07_f32")
-    g = _gpu_knn(c.X, c.k)
+    g = gpu_knn(c.X, c.k)
     ind = g["knn_idx"].cpu().numpy()
     d2 = g["knn_d2"].cpu().numpy()
     assert (ind[:, 0] == np.arange(ind.shape[0])).all()
@@ -93,7 +74,7 @@ def test_knn_lists_ordered_and_self_first():
 def test_graph_symmetric_sorted_and_weights():
     from tests import rows_ref as R
     c = Case("ns_epsauto_tau0p07_f32")
-    g = _gpu_knn(c.X, c.k, "auto")
+    g = gpu_knn(c.X, c.k, "auto")
     rp = g["row_ptr"].cpu().numpy()
     col = g["col"].cpu().numpy()
     w = g["w"].cpu().numpy()
@@ -124,13 +105,12 @@ def test_graph_symmetric_sorted_and_weights():
 
 def test_deterministic_bitwise():
     c = Case("ns_epsauto_tau0p0_i64")
-    U1, g1 = _run(c.X, c.Y.astype(np.int64), c.tau, c.eps, c.k, c.gbar)
-    U2, g2 = _run(c.X, c.Y.astype(np.int64), c.tau, c.eps, c.k, c.gbar)
+    U1, g1 = run_layer(c.X, c.Y.astype(np.int64), c.tau, c.eps, c.k, c.gbar)
+    U2, g2 = run_layer(c.X, c.Y.astype(np.int64), c.tau, c.eps, c.k, c.gbar)
     assert np.array_equal(U1, U2) and np.array_equal(g1, g2)
 
 
 def test_cpu_tensor_input_roundtrips_to_cpu():
-    GLL = _gll()
     c = Case("plumbing_eps1p0_tau0p07_f32")
     X = torch.from_numpy(c.X).requires_grad_(True)
     U = GLL.LaplaceLearningSparseHard.apply(X, torch.from_numpy(c.Y), c.tau, c.eps, c.k)
@@ -142,7 +122,6 @@ def test_cpu_tensor_input_roundtrips_to_cpu():
 
 
 def test_float64_and_noncontiguous_features():
-    GLL = _gll()
     c = Case("plumbing_epsauto_tau0p07_f32")
     wide = np.zeros((c.X.shape[0], 2 * c.X.shape[1]))
     wide[:, ::2] = c.X
@@ -161,8 +140,8 @@ def test_scalar_and_wide_feature_paths(d):
     X, lab = synth(60, 140, d, r=1.0, seed=5)
     Y = one_hot(lab[:60])
     g = seeded_gbar(140, 10, 7)
-    U, grad = _run(X, Y, 0.07, "auto", 8, g)
-    ind = _gpu_knn(X, 8)["knn_idx"].cpu().numpy()
+    U, grad = run_layer(X, Y, 0.07, "auto", 8, g)
+    ind = gpu_knn(X, 8)["knn_idx"].cpu().numpy()
     Uo, st = O.forward(X, Y, 0.07, "auto", 8, knn=(ind, None))
     assert O.rel_err(U, Uo) < TOL
     assert O.rel_err(grad, O.backward(st, g)) < TOL
@@ -180,8 +159,8 @@ def test_split_phase_gram_shapes(n, d, eps):
     X, lab = synth(base, n - base, d, r=1.0, seed=11)
     Y = one_hot(lab[:base])
     g = seeded_gbar(n - base, 10, 3)
-    U, grad = _run(X, Y, 0.07, eps, 10, g)
-    ind = _gpu_knn(X, 10, eps)["knn_idx"].cpu().numpy()
+    U, grad = run_layer(X, Y, 0.07, eps, 10, g)
+    ind = gpu_knn(X, 10, eps)["knn_idx"].cpu().numpy()
     assert O.knn_set_mismatch(X, ind, 10) == []
     Uo, st = O.forward(X, Y, 0.07, eps, 10, knn=(ind, None))
     assert O.rel_err(U, Uo) < TOL
@@ -202,8 +181,8 @@ def test_half_tile_gram_shapes(n, d, eps):
     X, lab = synth(base, n - base, d, r=1.0, latent=min(16, d), seed=13)
     Y = one_hot(lab[:base])
     g = seeded_gbar(n - base, 10, 5)
-    U, grad = _run(X, Y, 0.07, eps, 10, g)
-    ind = _gpu_knn(X, 10, eps)["knn_idx"].cpu().numpy()
+    U, grad = run_layer(X, Y, 0.07, eps, 10, g)
+    ind = gpu_knn(X, 10, eps)["knn_idx"].cpu().numpy()
     assert O.knn_set_mismatch(X, ind, 10) == []
     Uo, st = O.forward(X, Y, 0.07, eps, 10, knn=(ind, None))
     assert O.rel_err(U, Uo) < TOL
@@ -221,8 +200,8 @@ def test_candidate_capacity_boundaries(k, eps):
     X, lab = synth(120, 380, 64, r=1.0, seed=k)
     Y = one_hot(lab[:120])
     g = seeded_gbar(380, 10, k)
-    U, grad = _run(X, Y, 0.07, eps, k, g)
-    ind = _gpu_knn(X, k, eps)["knn_idx"].cpu().numpy()
+    U, grad = run_layer(X, Y, 0.07, eps, k, g)
+    ind = gpu_knn(X, k, eps)["knn_idx"].cpu().numpy()
     assert O.knn_set_mismatch(X, ind, k) == []
     Uo, st = O.forward(X, Y, 0.07, eps, k, knn=(ind, None))
     assert O.rel_err(U, Uo) < TOL
@@ -241,8 +220,8 @@ def test_tiny_graphs(n, base, k, eps):
     Y = one_hot(lab[:base])
     g = seeded_gbar(n - base, 10, 3)
     kk = min(k, n)
-    U, grad = _run(X, Y, 0.07, eps, k, g)
-    ind = _gpu_knn(X, kk, eps)["knn_idx"].cpu().numpy()
+    U, grad = run_layer(X, Y, 0.07, eps, k, g)
+    ind = gpu_knn(X, kk, eps)["knn_idx"].cpu().numpy()
     assert O.knn_set_mismatch(X, ind, kk) == []
     Uo, st = O.forward(X, Y, 0.07, eps, kk, knn=(ind, None))
     assert O.rel_err(U, Uo) < TOL
@@ -262,8 +241,8 @@ def test_odd_shapes(n, base, d, C, k, eps):
     lab = rng.integers(0, C, base)
     Y = np.eye(C, dtype=np.float32)[lab]
     g = rng.standard_normal((n - base, C))
-    U, grad = _run(X, Y, 0.07, eps, k, g)
-    ind = _gpu_knn(X, k, eps)["knn_idx"].cpu().numpy().astype(np.int64)
+    U, grad = run_layer(X, Y, 0.07, eps, k, g)
+    ind = gpu_knn(X, k, eps)["knn_idx"].cpu().numpy().astype(np.int64)
     assert O.knn_set_mismatch(X, ind, k) == []
     Uo, st = O.forward(X, Y, 0.07, eps, k, knn=(ind, None))
     assert U.shape == (n - base, C)
@@ -283,8 +262,8 @@ def test_wide_features_up_to_the_limit(d):
     lab = rng.integers(0, 10, base)
     Y = np.eye(10, dtype=np.float32)[lab]
     g = rng.standard_normal((n - base, 10))
-    U, grad = _run(X, Y, 0.07, 1.0, k, g)
-    ind = _gpu_knn(X, k, 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
+    U, grad = run_layer(X, Y, 0.07, 1.0, k, g)
+    ind = gpu_knn(X, k, 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
     assert O.knn_set_mismatch(X, ind, k) == []
     Uo, st = O.forward(X, Y, 0.07, 1.0, k, knn=(ind, None))
     assert O.rel_err(U, Uo) < TOL
@@ -297,12 +276,11 @@ def test_batch_of_one_equals_the_single_graph(eps):
     one: the same predictions and feature gradient (1e-5: the batched launch may run another CG
     geometry), U of shape [1, m, C]."""
     from graphlearninglayer_amd.synth import CONFIGS, one_hot, seeded_gbar, synth
-    GLL = _gll()
     c = CONFIGS["ns"]
     X, lab = synth(c["base"], c["batch"], c["d"], r=c["r"], seed=31)
     Y = one_hot(lab[: c["base"]])
     g = seeded_gbar(c["batch"], 10, 37)
-    U1, g1 = _run(X, Y, 0.07, eps, c["k"], g)
+    U1, g1 = run_layer(X, Y, 0.07, eps, c["k"], g)
     Xb = torch.from_numpy(X[None]).cuda().requires_grad_(True)
     Ub = GLL.LaplaceLearningSparseHard.apply(Xb, torch.from_numpy(Y[None]).cuda(), 0.07, eps,
                                              c["k"])
@@ -318,7 +296,6 @@ def test_batched_tiny_graphs(n, base, k):
     points): every graph's U and grad_X against the oracle on the GPU's own kNN lists, auto
     eps (GLL.py:14-177)."""
     from graphlearninglayer_amd.synth import one_hot, seeded_gbar, synth
-    GLL = _gll()
     B, kk = 3, min(k, n)
     Xs, Ys = [], []
     for g in range(B):
@@ -331,7 +308,7 @@ def test_batched_tiny_graphs(n, base, k):
     Ub = GLL.LaplaceLearningSparseHard.apply(Xb, torch.from_numpy(Ys).cuda(), 0.07, "auto", k)
     Ub.backward(torch.from_numpy(G).cuda())
     for g in range(B):
-        ind = _gpu_knn(Xs[g], kk, "auto")["knn_idx"].cpu().numpy().astype(np.int64)
+        ind = gpu_knn(Xs[g], kk, "auto")["knn_idx"].cpu().numpy().astype(np.int64)
         assert O.knn_set_mismatch(Xs[g], ind, kk) == []
         Uo, st = O.forward(Xs[g], Ys[g], tau=0.07, epsilon="auto", K=kk, knn=(ind, None))
         assert O.rel_err(Ub[g].detach().cpu().numpy(), Uo) <= TOL
@@ -349,8 +326,8 @@ def test_hub_row_longer_than_lds_chunk():
     base = 100
     Y = np.eye(10, dtype=np.float32)[lab[:base]]
     gb = rng.standard_normal((n - base, 10))
-    U, grad = _run(X, Y, 0.07, 1.0, 6, gb)
-    g = _gpu_knn(X, 6, 1.0)
+    U, grad = run_layer(X, Y, 0.07, 1.0, 6, gb)
+    g = gpu_knn(X, 6, 1.0)
     rp = g["row_ptr"].cpu().numpy()
     ind = g["knn_idx"].cpu().numpy()
     Uo, st = O.forward(X, Y, 0.07, 1.0, 6, knn=(ind, None))
@@ -377,8 +354,8 @@ def test_hub_row_overflow_within_lds_staging():
     lab = np.arange(n) % 10
     Y = np.eye(10, dtype=np.float32)[lab[:base]]
     gb = rng.standard_normal((n - base, 10))
-    U, grad = _run(X, Y, 0.07, 1.0, k, gb)
-    ind = _gpu_knn(X, k, 1.0)["knn_idx"].cpu().numpy()
+    U, grad = run_layer(X, Y, 0.07, 1.0, k, gb)
+    ind = gpu_knn(X, k, 1.0)["knn_idx"].cpu().numpy()
     rc = int((ind[:, 1:] == hub).sum())
     assert 8 * (k - 1) + 8 < rc <= 250, rc
     assert O.knn_set_mismatch(X, ind, k) == []
@@ -403,9 +380,9 @@ def test_duplicate_points_and_ties(k):
     lab = np.arange(n) % 10
     Y = np.eye(10, dtype=np.float32)[lab[:base]]
     gb = rng.standard_normal((n - base, 10))
-    U, grad = _run(X, Y, 0.07, 1.0, k, gb)
+    U, grad = run_layer(X, Y, 0.07, 1.0, k, gb)
     from graphlearninglayer_amd import _lib
-    g = _gpu_knn(X, k, 1.0)
+    g = gpu_knn(X, k, 1.0)
     ind = g["knn_idx"].cpu().numpy()
     assert int(g["status"][_lib.ST_KNN_MERGE].item()) > 0   # > 64 ties: the fallback ran
     assert O.knn_set_mismatch(X, ind, k) == []
@@ -416,7 +393,6 @@ def test_duplicate_points_and_ties(k):
 
 def test_no_labeled_rows_gives_zero_predictions():
     c = Case("plumbing_eps1p0_tau0p07_f32")
-    GLL = _gll()
     X = torch.from_numpy(c.X).cuda().requires_grad_(True)
     U = GLL.LaplaceLearningSparseHard.apply(X, torch.zeros(0, 10).cuda(), 0.07, 1.0, 5)
     assert U.shape == (128, 10) and torch.count_nonzero(U) == 0
@@ -424,7 +400,6 @@ def test_no_labeled_rows_gives_zero_predictions():
 
 def test_status_sink_raises_reference_warning():
     """Duplicate points make eps_i = 0 in auto mode: the reference warns (GLL.py:240-241)."""
-    GLL = _gll()
     c = Case("plumbing_epsauto_tau0p07_f32")
     GLL.check_status()
     X = c.X.copy()
@@ -442,7 +417,6 @@ def test_negative_epsilon_is_its_absolute_value():
     |eps| (plus the reference's 'very close to zero' style warning here): the native apply maps it
     to |eps| with a warning, U and grad_X bitwise those of |eps| and within 1e-4 of the oracle."""
     c = Case("ns_eps1p0_tau0p07_f32")
-    GLL = _gll()
     gb = np.random.default_rng(4).standard_normal(c.U.shape)
     outs = []
     for e in (-1.0, 1.0):
@@ -461,7 +435,6 @@ def test_negative_epsilon_is_its_absolute_value():
 
 
 def test_knn_sym_dist_mirror_matches_oracle():
-    GLL = _gll()
     c = Case("ns_epsauto_tau0p07_f32")
     W, V, mod_V, C, knn_ind = GLL.knn_sym_dist(c.X, k=c.k, epsilon="auto")
     assert np.array_equal(knn_ind, c.knn)
@@ -473,15 +446,14 @@ def test_knn_sym_dist_mirror_matches_oracle():
 
 def test_stable_conjgrad_mirror_reaches_float64_tolerance():
     import scipy.sparse as sp
-    GLL = _gll()
     rng = np.random.default_rng(1)
     m = 300
-    A = sp.random(m, m, density=0.02, random_state=2)
-    A = A + A.T
-    A = sp.diags(np.asarray(abs(A).sum(1)).ravel() + 0.5) - A
+    M = sp.random(m, m, density=0.02, random_state=2)
+    M = M + M.T
+    M = sp.diags(np.asarray(abs(M).sum(1)).ravel() + 0.5) - M
     b = rng.standard_normal((m, 3))
-    x = GLL.stable_conjgrad(A, b, tol=1e-10)
-    assert np.max(np.linalg.norm(b - A @ x, axis=0)) <= 1e-10
+    x = GLL.stable_conjgrad(M, b, tol=1e-10)
+    assert np.max(np.linalg.norm(b - M @ x, axis=0)) <= 1e-10
 
 
 def test_stress_shape_graph_parity():
@@ -491,8 +463,8 @@ def test_stress_shape_graph_parity():
     X, lab = synth(s["base"], s["batch"], s["d"], r=s["r"], seed=0)
     Y = one_hot(lab[: s["base"]])
     gb = seeded_gbar(s["batch"], 10)
-    U, grad = _run(X, Y, 0.07, "auto", s["k"], gb)
-    ind = _gpu_knn(X, s["k"])["knn_idx"].cpu().numpy()
+    U, grad = run_layer(X, Y, 0.07, "auto", s["k"], gb)
+    ind = gpu_knn(X, s["k"])["knn_idx"].cpu().numpy()
     rows = np.arange(0, X.shape[0], 128)
     # kNN: exact float64 distances of sampled rows
     X64 = X.astype(np.float64)
@@ -512,7 +484,6 @@ def test_stress_shape_graph_parity():
 def test_cpp_node_and_python_function_agree_bitwise():
     """The C++ autograd node (what .apply runs) and the ctypes Python Function are the
     same kernels: identical outputs and gradients."""
-    GLL = _gll()
     assert GLL._ext() is not None
     c = Case("ns_epsauto_tau0p07_f32")
     X = torch.from_numpy(c.X).cuda().requires_grad_(True)
@@ -528,7 +499,6 @@ def test_cpp_node_and_python_function_agree_bitwise():
 
 def test_output_does_not_alias_saved_state():
     """Callers edit the output in place (adversarial.py:691); backward must not change."""
-    GLL = _gll()
     c = Case("plumbing_eps1p0_tau0p07_f32")
     X = torch.from_numpy(c.X).cuda().requires_grad_(True)
     Y = torch.from_numpy(c.Y).cuda()
@@ -541,17 +511,6 @@ def test_output_does_not_alias_saved_state():
     assert torch.equal(ref, again)
 
 
-def _synth_batch(cfg, B, seed0=0):
-    from graphlearninglayer_amd.synth import CONFIGS, one_hot, synth
-    c = CONFIGS[cfg]
-    Xs, Ys = [], []
-    for g in range(B):
-        X, lab = synth(c["base"], c["batch"], c["d"], r=c["r"], seed=seed0 + g)
-        Xs.append(X)
-        Ys.append(one_hot(lab[: c["base"]]))
-    return np.stack(Xs), np.stack(Ys), c
-
-
 @pytest.mark.parametrize("cfg,eps,ydt,exact", [("plumbing", "auto", "i64", True),
                                                ("ns", 1.0, "f32", False),
                                                ("fullysup", 1.0, "f32", False)])
@@ -561,9 +520,8 @@ def test_batched_graphs_equal_single_calls_bitwise(cfg, eps, ydt, exact):
     graph (the unfused backward instead of cg_grad_fused_kernel, the batched select and
     gradient forms), so there the bar is 1e-5 relative (10x below the 1e-4 parity bar)."""
     from graphlearninglayer_amd.synth import seeded_gbar
-    GLL = _gll()
     B = 5
-    Xs, Ys, c = _synth_batch(cfg, B, seed0=11)
+    Xs, Ys, c = synth_batch(cfg, B, seed0=11)
     if ydt == "i64":
         Ys = Ys.astype(np.int64)
     G = np.stack([seeded_gbar(c["batch"], 10, 100 + g) for g in range(B)])
@@ -572,7 +530,7 @@ def test_batched_graphs_equal_single_calls_bitwise(cfg, eps, ydt, exact):
     assert Ub.shape == (B, c["batch"], 10) and Ub.dtype == torch.float64
     Ub.backward(torch.from_numpy(G).cuda())
     for g in range(B):
-        U1, gx1 = _run(Xs[g], Ys[g], 0.07, eps, c["k"], G[g])
+        U1, gx1 = run_layer(Xs[g], Ys[g], 0.07, eps, c["k"], G[g])
         if exact:
             np.testing.assert_array_equal(Ub[g].detach().cpu().numpy(), U1)
             np.testing.assert_array_equal(Xb.grad[g].cpu().numpy(), gx1)
@@ -587,14 +545,13 @@ def test_batched_auto_eps_matches_oracle(cfg, B):
     stress shape: every graph's U and grad_X against the float64 oracle on the GPU's own kNN
     lists, forward and adjoint (GLL.py:14-177)."""
     from graphlearninglayer_amd.synth import seeded_gbar
-    GLL = _gll()
-    Xs, Ys, c = _synth_batch(cfg, B, seed0=21)
+    Xs, Ys, c = synth_batch(cfg, B, seed0=21)
     G = np.stack([seeded_gbar(c["batch"], 10, 300 + g) for g in range(B)])
     Xb = torch.from_numpy(Xs).cuda().requires_grad_(True)
     Ub = GLL.LaplaceLearningSparseHard.apply(Xb, torch.from_numpy(Ys).cuda(), 0.07, "auto", c["k"])
     Ub.backward(torch.from_numpy(G).cuda())
     for g in range(B):
-        ind = _gpu_knn(Xs[g], c["k"], "auto")["knn_idx"].cpu().numpy().astype(np.int64)
+        ind = gpu_knn(Xs[g], c["k"], "auto")["knn_idx"].cpu().numpy().astype(np.int64)
         Uo, st = O.forward(Xs[g], Ys[g], tau=0.07, epsilon="auto", K=c["k"], knn=(ind, None))
         assert O.rel_err(Ub[g].detach().cpu().numpy(), Uo) <= TOL
         assert O.rel_err(Xb.grad[g].cpu().numpy(), O.backward(st, G[g])) <= TOL
@@ -604,7 +561,6 @@ def test_batched_duplicates_match_single_calls():
     """Batched selection (the occupancy form: x_i staged in LDS, 8 waves per SIMD) on graphs with
     > 64 tied candidates, where the full-row fallback runs: each graph's kNN, U and grad_X agree
     with its single call (the latency form)."""
-    GLL = _gll()
     rng = np.random.default_rng(8)
     n, d, base, k, B = 600, 40, 100, 10, 2
     Xs = rng.standard_normal((B, n, d)).astype(np.float32)
@@ -617,15 +573,14 @@ def test_batched_duplicates_match_single_calls():
     Ub = GLL.LaplaceLearningSparseHard.apply(Xb, torch.from_numpy(Y).cuda(), 0.07, 1.0, k)
     Ub.backward(torch.from_numpy(G).cuda())
     for g in range(B):
-        U1, gx1 = _run(Xs[g], Y, 0.07, 1.0, k, G[g])
+        U1, gx1 = run_layer(Xs[g], Y, 0.07, 1.0, k, G[g])
         assert O.rel_err(Ub[g].detach().cpu().numpy(), U1) <= 1e-5
         assert O.rel_err(Xb.grad[g].cpu().numpy(), gx1) <= 1e-5
 
 
 def test_batched_shared_labels_python_and_cpp_paths_agree():
-    GLL = _gll()
     B = 3
-    Xs, Ys, c = _synth_batch("plumbing", B, seed0=3)
+    Xs, Ys, c = synth_batch("plumbing", B, seed0=3)
     Y = torch.from_numpy(Ys[0]).cuda()            # one label matrix shared by the batch
     outs = []
     for fn in (GLL.LaplaceLearningSparseHard.apply, GLL.LaplaceLearningSparseHard.apply_python):
@@ -637,169 +592,9 @@ def test_batched_shared_labels_python_and_cpp_paths_agree():
     np.testing.assert_array_equal(outs[0][1], outs[1][1])
     # every graph against the float64 oracle on the GPU's own kNN lists
     for g in range(B):
-        ind = _gpu_knn(Xs[g], c["k"], 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
+        ind = gpu_knn(Xs[g], c["k"], 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
         Uo, _ = O.forward(Xs[g], Ys[0], tau=0.0, epsilon=1.0, K=c["k"], knn=(ind, None))
         assert O.rel_err(outs[0][0][g], Uo) <= TOL
-
-
-def _forward_c_abi(X, Y, k, tau, eps, flags=0, status=None):
-    """gll_forward through ctypes with explicit problem flags; returns (U, fwd iterations,
-    non-converged columns); `status` (a list) receives the public status words."""
-    import ctypes as ct
-    from graphlearninglayer_amd import _lib
-    GLL = _gll()
-    n, d = X.shape
-    base, C = Y.shape
-    prob = GLL.make_problem(n, d, base, C, k, tau, eps, flags=flags)
-    lib = _lib.lib()
-    ws = torch.empty(lib.gll_workspace_bytes(ct.byref(prob)), dtype=torch.uint8, device="cuda")
-    U = torch.empty(n - base, C, dtype=torch.float64, device="cuda")
-    Xd = torch.from_numpy(np.ascontiguousarray(X)).cuda()
-    Yd = torch.from_numpy(np.ascontiguousarray(Y)).cuda()
-    s = torch.cuda.current_stream().cuda_stream
-    _lib.check(lib.gll_forward(ct.byref(prob), Xd.data_ptr(), Yd.data_ptr(), _lib.GLL_DT_F32,
-                               ws.data_ptr(), U.data_ptr(), s), "gll_forward")
-    st = ws[: 4 * _lib.ST_NWORDS].view(torch.int32).cpu().tolist()
-    if status is not None:
-        status.extend(st)
-    return U.cpu().numpy(), st[_lib.ST_FWD_ITERS], st[_lib.ST_FWD_NONCONV]
-
-
-def test_grid_cg_forced_at_ns_matches_oracle():
-    """The whole-GPU cooperative CG (gridcg.hip) on the NS graph vs the float64 oracle."""
-    from graphlearninglayer_amd import _lib
-    from graphlearninglayer_amd.synth import CONFIGS, one_hot, synth
-    c = CONFIGS["ns"]
-    X, lab = synth(c["base"], c["batch"], c["d"], r=c["r"], seed=0)
-    Y = one_hot(lab[: c["base"]])
-    Ug, itg, ncg = _forward_c_abi(X, Y, c["k"], 0.07, 1.0, flags=_lib.FLAG_CG_GRID)
-    Ue, ite, nce = _forward_c_abi(X, Y, c["k"], 0.07, 1.0)
-    # (iteration counts differ by preconditioner: the register-ELL kernel runs the Neumann
-    # form at NS, about half the Jacobi iterations of the whole-GPU kernel)
-    assert ncg == 0 and nce == 0 and itg > 0 and ite > 0
-    ind = _gpu_knn(X, c["k"], 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
-    Uo, _ = O.forward(X, Y, tau=0.07, epsilon=1.0, K=c["k"], knn=(ind, None))
-    assert O.rel_err(Ug, Uo) <= TOL
-    assert O.rel_err(Ug, Ue) <= 1e-5
-
-
-def test_grid_cg_large_system_fwd_bwd_matches_oracle():
-    """m = 6000 > 4096 selects the grid CG automatically (forward and adjoint)."""
-    from graphlearninglayer_amd.synth import one_hot, seeded_gbar, synth
-    base, m, d, k = 2000, 6000, 64, 10
-    X, lab = synth(base, m, d, r=1.0, seed=5)
-    Y = one_hot(lab[:base])
-    g = seeded_gbar(m, 10, 7)
-    U, grad = _run(X, Y, 0.07, 1.0, k, g)
-    ind = _gpu_knn(X, k, 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
-    Uo, st = O.forward(X, Y, tau=0.07, epsilon=1.0, K=k, knn=(ind, None))
-    go = O.backward(st, g)
-    assert O.rel_err(U, Uo) <= TOL
-    assert O.rel_err(grad, go) <= TOL
-
-
-def test_cg_csr_large_matches_scipy():
-    """gll_cg_csr for m > 2048 (grid CG) against a direct sparse solve."""
-    import scipy.sparse as sp
-    import scipy.sparse.linalg as spla
-    GLL = _gll()
-    rng = np.random.default_rng(3)
-    m, C = 5000, 4
-    A = sp.random(m, m, density=6.0 / m, random_state=rng, format="csr")
-    A = A + A.T
-    A = (sp.diags(np.asarray(abs(A).sum(1)).ravel() + 0.5) + A).tocsr()   # SPD, dominant
-    b = rng.standard_normal((m, C))
-    x = GLL.stable_conjgrad(A, b, tol=1e-8)
-    xe = spla.spsolve(A.tocsc(), b)
-    assert np.max(np.abs(x - xe)) <= 1e-6 * np.max(np.abs(xe))
-
-
-@pytest.mark.parametrize("fname", ["laplace_small", "laplace_k64"])
-def test_utils_laplace_matches_reference_fixture(fname):
-    """utils.laplace on the GPU vs the reference pipeline's fixture
-    (laplace_k64: knn_num = 64, the wide kNN select, pinned by the reference itself)."""
-    import json
-    import os
-    from graphlearninglayer_amd import utils as U_
-    from graphlearninglayer_amd.synth import synth
-    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
-                             fname + ".npz"))
-    p = json.loads(str(z["meta"]))
-    X, labels = synth(p["labeled"], p["unlabeled"], p["d"], C=10, r=p["r"], seed=p["seed"])
-    train = labels[: p["labeled"]]
-    U = U_.laplace(X, train, knn_num=p["knn_num"], epsilon=p["epsilon"], tau=p["tau"])
-    assert U.shape == z["U"].shape and U.dtype == np.float64
-    ind = _gpu_knn(X, p["knn_num"], p["epsilon"])["knn_idx"].cpu().numpy().astype(np.int64)
-    Uo = O.laplace(X, train, knn_num=p["knn_num"], epsilon=p["epsilon"], tau=p["tau"],
-                   knn=(ind, None))
-    assert O.rel_err(U, Uo) <= TOL
-    ref_ind = z["knn"].astype(np.int64)
-    bad = [i for i, (a, b) in enumerate(zip(ind.tolist(), ref_ind.tolist())) if set(a) != set(b)]
-    assert bad == [], f"{len(bad)} rows differ from the reference kNN, first {bad[:8]}"
-    assert O.rel_err(U, z["U"]) <= TOL          # against the reference pipeline's output
-    assert np.mean(U.argmax(1) == z["U"].argmax(1)) >= 0.999
-
-
-def test_utils_laplace_large_graph_matches_oracle():
-    """n = 20,250 (250 labeled), d = 128, k = 50: the whole-GPU CG + float64 refinement."""
-    from graphlearninglayer_amd import utils as U_
-    from graphlearninglayer_amd.synth import synth
-    X, labels = synth(250, 20000, 128, C=10, r=1.0, seed=8)
-    train = labels[:250]
-    U = U_.laplace(X, train, knn_num=50, epsilon=1.0, tau=1e-8)
-    ind = _gpu_knn(X, 50, 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
-    Uo = O.laplace(X, train, knn_num=50, epsilon=1.0, tau=1e-8, knn=(ind, None))
-    assert O.rel_err(U, Uo) <= TOL
-    acc = U_.gl_accuracy(X[:250], train, X[250:], labels[250:])
-    assert acc == pytest.approx(100.0 * np.mean(Uo.argmax(1) == labels[250:]), abs=0.05)
-
-
-def test_utils_laplace_reference_size_properties():
-    """utils.laplace at the reference's evaluation size (250 labeled + 50,000 unlabeled train +
-    10,000 test, d = 128, k = 50, utils.py:570-593): too large for the SuperLU oracle, so
-    size-independent properties instead.  (1) kNN lists of 64 sampled rows equal the exact
-    float64 sets over all 60,250 points; (2) the reference's own stopping criterion holds in
-    float64 on the host, recomputed from the GPU graph: max_c ||M (rhs - Luu x)|| <= 1e-10 with
-    M = diag(Luu + 1e-10)^(-1/2) (utils.py:586-591, GLL.py:259); (3) every prediction row is
-    a convex combination of the labels (rows sum to 1, entries in [0, 1], maximum principle)."""
-    import scipy.sparse as sp
-    from graphlearninglayer_amd import utils as U_
-    from graphlearninglayer_amd.synth import synth
-    nl, nu, k = 250, 60000, 50
-    X, labels = synth(nl, nu, 128, C=10, r=1.0, seed=3)
-    Xd = torch.from_numpy(X).cuda()
-    U = U_.laplace(Xd, labels[:nl], knn_num=k, epsilon=1.0, tau=1e-8)
-    n, m = nl + nu, nu
-    assert U.shape == (m, 10) and np.isfinite(U).all()
-    g = _gpu_knn(X, k, 1.0)
-    ind = g["knn_idx"].cpu().numpy()
-    rng = np.random.default_rng(0)
-    X64 = X.astype(np.float64)
-    for i in rng.choice(n, 64, replace=False):
-        d2 = np.sum((X64 - X64[i]) ** 2, axis=1)
-        order = np.argsort(d2, kind="stable")
-        gap = d2[order[k]] - d2[order[k - 1]]
-        if gap > 1e-12 * max(d2[order[k]], 1e-30):     # no exact tie at the boundary
-            assert set(ind[i].tolist()) == set(order[:k].tolist()), f"row {i}"
-    rp, col = g["row_ptr"].cpu().numpy(), g["col"].cpu().numpy()
-    W = sp.csr_matrix((g["w"].cpu().numpy().astype(np.float64), col, rp), shape=(n, n))
-    deg = np.asarray(W.sum(axis=1)).ravel()
-    L = (sp.diags(deg) - W).tocsr()
-    Luu = L[nl:, nl:] + 1e-8 * sp.eye(m)
-    Y = U_.one_hot_encode(labels[:nl])
-    rhs = -(L[nl:, :nl] @ Y)
-    Mv = 1.0 / np.sqrt(Luu.diagonal() + 1e-10)
-    res = np.linalg.norm(Mv[:, None] * (rhs - Luu @ U), axis=0)
-    assert res.max() <= 2e-10, f"scaled residual {res.max():.3e}"
-    # Luu is an M-matrix and W_ul Y >= 0, so 0 <= U and U 1 = 1 - tau Luu^-1 1 <= 1
-    assert U.min() >= -1e-7 and U.sum(1).max() <= 1.0 + 1e-7
-    acc = 100.0 * np.mean(U.argmax(1) == labels[nl:])
-    print(f"n={n}: scaled residual {res.max():.2e}, GL accuracy {acc:.2f}%")
-
-
-def _exact_knn_rows(X, ind, k):
-    """Rows whose GPU kNN set differs from the exact float64 set (ties at 1e-12 excused)."""
-    return O.knn_set_mismatch(X, ind, k, rel_gap=1e-12)
 
 
 @pytest.mark.parametrize("offset", [100.0, 1000.0])
@@ -813,11 +608,11 @@ def test_translated_features_exact_knn(offset):
     rng = np.random.default_rng(17)
     v = rng.standard_normal(c.X.shape[1])
     Xs = (c.X.astype(np.float64) + offset * v / np.linalg.norm(v)).astype(np.float32)
-    g = _gpu_knn(Xs, c.k, c.eps)
+    g = gpu_knn(Xs, c.k, c.eps)
     ind = g["knn_idx"].cpu().numpy()
-    assert _exact_knn_rows(Xs, ind, c.k) == []
+    assert exact_knn_rows(Xs, ind, c.k) == []
     assert int(g["status"][_lib.ST_KNN_RESCAN].item()) == 0
-    U, grad = _run(Xs, c.Y, c.tau, c.eps, c.k, c.gbar)
+    U, grad = run_layer(Xs, c.Y, c.tau, c.eps, c.k, c.gbar)
     Uo, st = O.forward(Xs, c.Y, c.tau, c.eps, c.k, knn=(ind.astype(np.int64), None))
     assert O.rel_err(U, Uo) < TOL
     assert O.rel_err(grad, O.backward(st, c.gbar)) < TOL
@@ -833,13 +628,13 @@ def test_far_centre_row_takes_exact_rescan():
     X = X.astype(np.float32)
     X[0] = 300.0 / np.sqrt(64)      # |x_0 - x_i| ~ 300
     k = 10
-    g = _gpu_knn(X, k, "auto")
+    g = gpu_knn(X, k, "auto")
     ind = g["knn_idx"].cpu().numpy()
     assert int(g["status"][_lib.ST_KNN_RESCAN].item()) > 100
-    assert _exact_knn_rows(X, ind, k) == []
+    assert exact_knn_rows(X, ind, k) == []
     Y = one_hot(lab[:100])
     gb = seeded_gbar(400, 10, 5)
-    U, grad = _run(X, Y, 0.07, "auto", k, gb)
+    U, grad = run_layer(X, Y, 0.07, "auto", k, gb)
     Uo, st = O.forward(X, Y, 0.07, "auto", k, knn=(ind.astype(np.int64), None))
     assert O.rel_err(U, Uo) < TOL
     assert O.rel_err(grad, O.backward(st, gb)) < TOL
@@ -851,290 +646,8 @@ def test_knn_exact_against_float64(cfg):
     from graphlearninglayer_amd.synth import CONFIGS, synth
     c = CONFIGS[cfg]
     X, _ = synth(c["base"], c["batch"], c["d"], r=c["r"], seed=3)
-    ind = _gpu_knn(X, c["k"], 1.0)["knn_idx"].cpu().numpy()
-    assert _exact_knn_rows(X, ind, c["k"]) == []
-
-
-def _grid_case():
-    from graphlearninglayer_amd.synth import one_hot, synth
-    base, m, d, k = 2000, 6000, 64, 10
-    X, lab = synth(base, m, d, r=1.0, seed=5)
-    return X, one_hot(lab[:base]), k
-
-
-def test_grid_cg_oversubscribed_launch_is_refused():
-    """A whole-GPU CG grid larger than the co-resident capacity is refused at launch (the
-    cooperative launch's guarantee) and surfaces as an error -- never as a U computed by a
-    grid whose barrier waited on workgroups that were not resident."""
-    from graphlearninglayer_amd import _lib
-    X, Y, k = _grid_case()
-    with pytest.raises(RuntimeError, match="gll_forward failed"):
-        _forward_c_abi(X, Y, k, 0.07, 1.0, flags=_lib.FLAG_CG_GRID | _lib.FLAG_DIAG_GRID_OVERSUB)
-    torch.cuda.synchronize()   # the device is still healthy: a normal call works
-    U, it, nc = _forward_c_abi(X, Y, k, 0.07, 1.0)
-    assert np.isfinite(U).all() and nc == 0
-
-
-def test_grid_cg_sync_words_reset_between_solves():
-    """The whole-GPU CG's sync words are zeroed by row_build before a forward and returned to
-    zero by the last workgroup out of every solve (gridcg.hip gv_exit) -- no memset launch.  Three
-    backward calls on one workspace after a forward give bitwise equal gradients with no failed
-    or rescued barrier; after a forward whose barrier failed (injected: the rescue solve ran), a
-    normal backward on the same workspace runs its grid solve cleanly (GLL.py:53,93)."""
-    import ctypes as ct
-    from graphlearninglayer_amd import _lib
-    from graphlearninglayer_amd.synth import seeded_gbar
-    X, Y, k = _grid_case()
-    n, d = X.shape
-    base, C = Y.shape
-    g = seeded_gbar(n - base, C, 3)
-    U, grads, st = _fwd_bwds_c_abi(X, Y, k, 0.07, 1.0, g, backward_calls=3)
-    for gx in grads[1:]:
-        np.testing.assert_array_equal(gx, grads[0])
-    assert st[_lib.ST_SOLVE_FAILED] == 0 and st[_lib.ST_GRID_RESCUED] == 0
-    GLL = _gll()
-    lib = _lib.lib()
-    pf = GLL.make_problem(n, d, base, C, k, 0.07, 1.0, flags=_lib.FLAG_DIAG_GRID_FAIL)
-    pn = GLL.make_problem(n, d, base, C, k, 0.07, 1.0)
-    assert lib.gll_workspace_bytes(ct.byref(pf)) == lib.gll_workspace_bytes(ct.byref(pn))
-    ws = torch.empty(lib.gll_workspace_bytes(ct.byref(pn)), dtype=torch.uint8, device="cuda")
-    Ud = torch.empty(n - base, C, dtype=torch.float64, device="cuda")
-    gx = torch.empty(n, d, dtype=torch.float32, device="cuda")
-    Xd = torch.from_numpy(np.ascontiguousarray(X)).cuda()
-    Yd = torch.from_numpy(np.ascontiguousarray(Y)).cuda()
-    Gd = torch.from_numpy(np.ascontiguousarray(g)).cuda()
-    s = torch.cuda.current_stream().cuda_stream
-    _lib.check(lib.gll_forward(ct.byref(pf), Xd.data_ptr(), Yd.data_ptr(), _lib.GLL_DT_F32,
-                               ws.data_ptr(), Ud.data_ptr(), s), "gll_forward")
-    rescued = int(ws[: 4 * _lib.ST_NWORDS].view(torch.int32)[_lib.ST_GRID_RESCUED].item())
-    assert rescued >= 1
-    _lib.check(lib.gll_backward(ct.byref(pn), Xd.data_ptr(), None, 0, ws.data_ptr(),
-                                Gd.data_ptr(), _lib.GLL_DT_F64, gx.data_ptr(), s), "gll_backward")
-    st2 = ws[: 4 * _lib.ST_NWORDS].view(torch.int32).cpu().tolist()
-    assert st2[_lib.ST_GRID_RESCUED] == rescued and st2[_lib.ST_SOLVE_FAILED] == 0
-    assert O.rel_err(Ud.cpu().numpy(), U) <= 1e-5
-    assert O.rel_err(gx.cpu().numpy(), grads[0]) <= 1e-5
-
-
-def test_grid_cg_barrier_failure_is_rescued():
-    """An (injected) grid-barrier failure of the whole-GPU CG (gridcg.hip): the first workgroup
-    to see it solves the system alone (rescue_solve) and the others write nothing -- U still
-    matches the float64 oracle, GLL_ST_GRID_RESCUED counts the rescue and is reported as a
-    RuntimeWarning, and no error is raised (GLL.py:53)."""
-    from graphlearninglayer_amd import _lib
-    GLL = _gll()
-    X, Y, k = _grid_case()
-    st = []
-    U, it, nc = _forward_c_abi(X, Y, k, 0.07, 1.0,
-                               flags=_lib.FLAG_CG_GRID | _lib.FLAG_DIAG_GRID_FAIL, status=st)
-    assert st[_lib.ST_GRID_RESCUED] == 1 and st[_lib.ST_SOLVE_FAILED] == 0 and nc == 0
-    ind = _gpu_knn(X, k, 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
-    Uo, _ = O.forward(X, Y, tau=0.07, epsilon=1.0, K=k, knn=(ind, None))
-    assert O.rel_err(U, Uo) <= TOL
-    with pytest.warns(RuntimeWarning, match="solved by one workgroup"):
-        GLL._warn_from(st)
-
-
-def test_grid_cg_correct_beside_a_kernel_holding_the_cus():
-    """The whole-GPU CG launches ordinarily (no cooperative residency promise).  With a large
-    GEMM holding the CUs on another stream when the stress solve starts, its workgroups become
-    resident as the GEMM's retire; the solve completes (or is rescued) and U and grad_X match
-    the float64 oracle (GLL.py:53,93)."""
-    from graphlearninglayer_amd.synth import CONFIGS, one_hot, seeded_gbar, synth
-    c = CONFIGS["stress"]
-    X, lab = synth(c["base"], c["batch"], c["d"], r=c["r"], seed=8)
-    Y = one_hot(lab[: c["base"]])
-    g = seeded_gbar(c["batch"], 10, 9)
-    a = torch.randn(8192, 8192, device="cuda")
-    side = torch.cuda.Stream()
-    torch.cuda.synchronize()
-    with torch.cuda.stream(side):
-        for _ in range(4):
-            a = a @ a * 1e-4   # ~tens of ms of GEMM on every CU
-    U, grad = _run(X, Y, 0.07, "auto", c["k"], g)
-    torch.cuda.synchronize()
-    ind = _gpu_knn(X, c["k"])["knn_idx"].cpu().numpy()
-    Uo, st = O.forward(X, Y, 0.07, "auto", c["k"], knn=(ind, None))
-    assert O.rel_err(U, Uo) < TOL
-    assert O.rel_err(grad, O.backward(st, g)) < TOL
-
-
-def test_grid_cg_past_capacity_falls_back_to_per_column(monkeypatch):
-    """More rows than the co-resident workgroups can hold (capacity shrunk to 4 workgroups
-    through the GLL_KNOB_GRID_CAP test knob): the whole-GPU CG declines and the per-column kernels with the
-    Krylov vectors in the workspace solve the system -- no size limit, same answer."""
-    X, Y, k = _grid_case()
-    from graphlearninglayer_amd import _lib
-    _lib.set_knob(_lib.KNOB_GRID_CAP, 4)
-    try:
-        U, it, nc = _forward_c_abi(X, Y, k, 0.07, 1.0)
-    finally:
-        _lib.set_knob(_lib.KNOB_GRID_CAP, 0)
-    ind = _gpu_knn(X, k, 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
-    Uo, _ = O.forward(X, Y, tau=0.07, epsilon=1.0, K=k, knn=(ind, None))
-    assert nc == 0 and O.rel_err(U, Uo) <= TOL
-
-
-@pytest.mark.parametrize("cfg,flags", [("fullysup", 0), ("ns", "vr"), ("plumbing", "vr")])
-def test_balanced_cg_matches_register_ell_and_oracle(cfg, flags):
-    """The balanced virtual-row CG (solve.hip cg_vr_kernel: the automatic choice at K = 25, the
-    FullySup shape; forced elsewhere) against the register-ELL kernel and the float64 oracle,
-    forward and adjoint (GLL.py:53,93)."""
-    from graphlearninglayer_amd import _lib
-    from graphlearninglayer_amd.synth import CONFIGS, one_hot, synth
-    c = CONFIGS[cfg]
-    X, lab = synth(c["base"], c["batch"], c["d"], r=c["r"], seed=2)
-    Y = one_hot(lab[: c["base"]])
-    fv = _lib.FLAG_CG_VR if flags == "vr" else 0
-    st_v, st_e = [], []
-    Uv, itv, ncv = _forward_c_abi(X, Y, c["k"], 0.07, 1.0, flags=fv, status=st_v)
-    Ue, ite, nce = _forward_c_abi(X, Y, c["k"], 0.07, 1.0, flags=_lib.FLAG_CG_ELL, status=st_e)
-    assert ncv == 0 and nce == 0 and itv > 0 and ite > 0, (itv, ite)   # Jacobi vs Neumann
-    ind = _gpu_knn(X, c["k"], 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
-    Uo, _ = O.forward(X, Y, tau=0.07, epsilon=1.0, K=c["k"], knn=(ind, None))
-    assert O.rel_err(Uv, Uo) <= TOL
-    assert O.rel_err(Uv, Ue) <= 1e-5
-
-
-def test_balanced_cg_spill_path_matches_oracle(monkeypatch):
-    """Virtual rows past the register capacity (forced to 4 per thread through the GLL_KNOB_VR_RV test knob, so
-    most of the FullySup U block spills) are summed from the CSR by their rows' threads: same
-    answer, forward and adjoint, deterministic."""
-    from graphlearninglayer_amd.synth import CONFIGS, one_hot, seeded_gbar, synth
-    c = CONFIGS["fullysup"]
-    X, lab = synth(c["base"], c["batch"], c["d"], r=c["r"], seed=4)
-    Y = one_hot(lab[: c["base"]])
-    g = seeded_gbar(c["batch"], 10, 9)
-    from graphlearninglayer_amd import _lib
-    _lib.set_knob(_lib.KNOB_VR_RV, 4)
-    try:
-        U1, gr1 = _run(X, Y, 0.07, 1.0, c["k"], g)
-        U2, gr2 = _run(X, Y, 0.07, 1.0, c["k"], g)
-    finally:
-        _lib.set_knob(_lib.KNOB_VR_RV, 0)
-    np.testing.assert_array_equal(U1, U2)
-    np.testing.assert_array_equal(gr1, gr2)
-    ind = _gpu_knn(X, c["k"], 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
-    Uo, st = O.forward(X, Y, tau=0.07, epsilon=1.0, K=c["k"], knn=(ind, None))
-    assert O.rel_err(U1, Uo) <= TOL
-    assert O.rel_err(gr1, O.backward(st, g)) <= TOL
-
-
-def test_balanced_cg_vrm_clamp_at_wide_k_matches_oracle():
-    """Advisor (round 5): at k = 129 a U row may need ceil((5(K-1)+8)/8) = 81 virtual-row slots,
-    past the 63 the CG's 6-bit slot field holds (vr_max_per_row clamps), so long rows keep their
-    tail in the CSR.  Forcing the balanced kernel (GLL_FLAG_CG_VR, 10 virtual rows per thread)
-    at k = 129 runs the clamp and the spill path together; forward and adjoint against the
-    oracle."""
-    from graphlearninglayer_amd import _lib
-    from graphlearninglayer_amd.synth import one_hot, seeded_gbar, synth
-    X, lab = synth(500, 500, 64, C=10, r=1.0, seed=6)
-    Y = one_hot(lab[:500])
-    g = seeded_gbar(500, 10, 5)
-    _lib.set_knob(_lib.KNOB_VR_RV, 10)
-    try:
-        U, gr = _fwd_bwd_c_abi(X, Y, 129, 0.07, 1.0, g, flags=_lib.FLAG_CG_VR)
-    finally:
-        _lib.set_knob(_lib.KNOB_VR_RV, 0)
-    ind = _gpu_knn(X, 129, 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
-    Uo, st = O.forward(X, Y, tau=0.07, epsilon=1.0, K=129, knn=(ind, None))
-    assert O.rel_err(U, Uo) <= TOL
-    assert O.rel_err(gr, O.backward(st, g)) <= TOL
-
-
-def _nan(*shape, dtype):
-    """An output buffer no kernel has written: NaN everywhere (a caching-allocator block from
-    torch.empty usually still holds the previous, correct result of the same shape)."""
-    return torch.full(shape, float("nan"), dtype=dtype, device="cuda")
-
-
-def _fwd_bwd_c_abi(X, Y, k, tau, eps, gbar, flags=0, bwd_flags=None, ws_fill=None, counts=False):
-    """gll_forward + gll_backward through ctypes with explicit problem flags: (U, grad_X), both
-    written into NaN-filled buffers.  `bwd_flags`: the backward's own flags (default: the
-    forward's); `ws_fill`: a byte value the workspace holds before the forward (default:
-    torch.empty's contents); `counts`: also return the backward's launches
-    (tests/launch_counts.py)."""
-    import ctypes as ct
-    from graphlearninglayer_amd import _lib
-    GLL = _gll()
-    n, d = X.shape
-    base, C = Y.shape
-    prob = GLL.make_problem(n, d, base, C, k, tau, eps, flags=flags)
-    bprob = prob if bwd_flags is None else GLL.make_problem(n, d, base, C, k, tau, eps,
-                                                            flags=bwd_flags)
-    lib = _lib.lib()
-    ws = torch.empty(lib.gll_workspace_bytes(ct.byref(prob)), dtype=torch.uint8, device="cuda")
-    if ws_fill is not None:
-        ws.fill_(ws_fill)
-    U = _nan(n - base, C, dtype=torch.float64)
-    gx = _nan(n, d, dtype=torch.float32)
-    Xd = torch.from_numpy(np.ascontiguousarray(X)).cuda()
-    Yd = torch.from_numpy(np.ascontiguousarray(Y)).cuda()
-    gd = torch.from_numpy(np.ascontiguousarray(gbar, dtype=np.float64)).cuda()
-    s = torch.cuda.current_stream().cuda_stream
-    _lib.check(lib.gll_forward(ct.byref(prob), Xd.data_ptr(), Yd.data_ptr(), _lib.GLL_DT_F32,
-                               ws.data_ptr(), U.data_ptr(), s), "gll_forward")
-    import contextlib
-    from tests.launch_counts import counted
-    with (counted() if counts else contextlib.nullcontext()) as got:
-        _lib.check(lib.gll_backward(ct.byref(bprob), Xd.data_ptr(), Yd.data_ptr(),
-                                    _lib.GLL_DT_F32, ws.data_ptr(), gd.data_ptr(),
-                                    _lib.GLL_DT_F64, gx.data_ptr(), s), "gll_backward")
-    torch.cuda.synchronize()
-    if counts:
-        return U.cpu().numpy(), gx.cpu().numpy(), got
-    return U.cpu().numpy(), gx.cpu().numpy()
-
-
-def _fwd_bwd_batched_c_abi(Xs, Ys, k, tau, eps, G, flags=0, ws=None):
-    """gll_forward_batched + gll_backward_batched through ctypes: (U[B], grad_X[B]), both
-    written into NaN-filled buffers.  `ws`: a workspace to reuse (default: a fresh torch.empty
-    one)."""
-    import ctypes as ct
-    from graphlearninglayer_amd import _lib
-    GLL = _gll()
-    B, n, d = Xs.shape
-    base, C = Ys.shape[1:]
-    prob = GLL.make_problem(n, d, base, C, k, tau, eps, flags=flags)
-    lib = _lib.lib()
-    wb = lib.gll_workspace_bytes(ct.byref(prob))
-    if ws is None:
-        ws = torch.empty(B * wb, dtype=torch.uint8, device="cuda")
-    assert ws.numel() >= B * wb
-    U = _nan(B, n - base, C, dtype=torch.float64)
-    gx = _nan(B, n, d, dtype=torch.float32)
-    Xd = torch.from_numpy(np.ascontiguousarray(Xs)).cuda()
-    Yd = torch.from_numpy(np.ascontiguousarray(Ys)).cuda()
-    gd = torch.from_numpy(np.ascontiguousarray(G, dtype=np.float64)).cuda()
-    s = torch.cuda.current_stream().cuda_stream
-    _lib.check(lib.gll_forward_batched(ct.byref(prob), B, Xd.data_ptr(), Yd.data_ptr(),
-                                       _lib.GLL_DT_F32, ws.data_ptr(), U.data_ptr(), s),
-               "gll_forward_batched")
-    _lib.check(lib.gll_backward_batched(ct.byref(prob), B, Xd.data_ptr(), ws.data_ptr(),
-                                        gd.data_ptr(), _lib.GLL_DT_F64, gx.data_ptr(), s),
-               "gll_backward_batched")
-    torch.cuda.synchronize()
-    return U.cpu().numpy(), gx.cpu().numpy(), ws, prob
-
-
-def _batched_knn_lists(ws, prob, B):
-    """Each graph's kNN list (n x K int32) read from its block of a batched workspace (the lists
-    the batched select kernel itself wrote), via gll_workspace_view."""
-    import ctypes as ct
-    from graphlearninglayer_amd import _lib
-    lib = _lib.lib()
-    wb = lib.gll_workspace_bytes(ct.byref(prob))
-    out = []
-    for g in range(B):
-        view = _lib.View()
-        base = ws.data_ptr() + g * wb
-        _lib.check(lib.gll_workspace_view(ct.byref(prob), base, ct.byref(view)),
-                   "gll_workspace_view")
-        off = view.knn_idx - ws.data_ptr()
-        cnt = prob.n * prob.K
-        out.append(ws[off: off + 4 * cnt].view(torch.int32).reshape(prob.n, prob.K)
-                   .cpu().numpy().astype(np.int64))
-    return out
+    ind = gpu_knn(X, c["k"], 1.0)["knn_idx"].cpu().numpy()
+    assert exact_knn_rows(X, ind, c["k"]) == []
 
 
 @pytest.mark.parametrize("d,eps", [(64, 1.0), (256, "auto"), (100, "auto")])
@@ -1148,7 +661,6 @@ def test_knn_row_panels_match_whole_matrix(d, eps):
     from graphlearninglayer_amd.synth import one_hot, seeded_gbar, synth
     base, m, k = 900, 3300, 10
     X, lab = synth(base, m, d, r=1.0, seed=31)
-    GLL = _gll()
     Xd = torch.from_numpy(X).cuda()
     gw = GLL.device_graph(Xd, k, eps)
     gp = GLL.device_graph(Xd, k, eps, flags=_lib.FLAG_KNN_PANEL)
@@ -1156,8 +668,8 @@ def test_knn_row_panels_match_whole_matrix(d, eps):
         assert torch.equal(gw[key], gp[key]), key
     Y = one_hot(lab[:base])
     g = seeded_gbar(m, 10, 77)
-    Uw, gxw = _fwd_bwd_c_abi(X, Y, k, 0.07, eps, g)
-    Up, gxp = _fwd_bwd_c_abi(X, Y, k, 0.07, eps, g, flags=_lib.FLAG_KNN_PANEL)
+    Uw, gxw = fwd_bwd_c_abi(X, Y, k, 0.07, eps, g)
+    Up, gxp = fwd_bwd_c_abi(X, Y, k, 0.07, eps, g, flags=_lib.FLAG_KNN_PANEL)
     np.testing.assert_array_equal(Up, Uw)
     np.testing.assert_array_equal(gxp, gxw)
 
@@ -1172,8 +684,8 @@ def test_knn_row_panels_automatic_past_the_n2_buffer():
     rng = np.random.default_rng(5)
     centres = rng.standard_normal((50, d))
     X = (centres[rng.integers(0, 50, n)] + 0.6 * rng.standard_normal((n, d))).astype(np.float32)
-    GLL = _gll()
     prob = GLL.make_problem(n, d, 0, 1, k, 0.0, "auto")
+    # the raw call: the size itself is the subject, and no 100,000-row Run is wanted for it
     nbytes = _lib.lib().gll_workspace_bytes(ct.byref(prob))
     assert nbytes < n * n * 4 // 4, nbytes
     g = GLL.device_graph(torch.from_numpy(X).cuda(), k, "auto")
@@ -1205,20 +717,17 @@ def test_fp16_distance_storage_matches_fp32(cfg, B, scale):
     batched tests hold to single calls and the oracle."""
     from graphlearninglayer_amd import _lib
     from graphlearninglayer_amd.synth import seeded_gbar
-    Xs, Ys, c = _synth_batch(cfg, B, seed0=61)
+    Xs, Ys, c = synth_batch(cfg, B, seed0=61)
     Xs = (Xs * scale).astype(np.float32)
     G = np.stack([seeded_gbar(c["batch"], 10, 700 + g) for g in range(B)])
     eps = "auto"
-    Uh, gh = _fwd_bwd_batched_c_abi(Xs, Ys, c["k"], 0.07, eps, G)[:2]
-    Uf, gf = _fwd_bwd_batched_c_abi(Xs, Ys, c["k"], 0.07, eps, G, flags=_lib.FLAG_D2_F32)[:2]
+    Uh, gh = fwd_bwd_batched_c_abi(Xs, Ys, c["k"], 0.07, eps, G)[:2]
+    Uf, gf = fwd_bwd_batched_c_abi(Xs, Ys, c["k"], 0.07, eps, G, flags=_lib.FLAG_D2_F32)[:2]
     np.testing.assert_array_equal(Uh, Uf)
     np.testing.assert_array_equal(gh, gf)
     if scale != 1.0:   # one workspace, first a batch at 1/scale of these features, then these
-        import ctypes as ct
-        prob = _gll().make_problem(Xs.shape[1], Xs.shape[2], Ys.shape[1], Ys.shape[2], c["k"], 0.07, eps)
-        ws = torch.empty(B * _lib.lib().gll_workspace_bytes(ct.byref(prob)), dtype=torch.uint8, device="cuda")
-        _fwd_bwd_batched_c_abi((Xs / scale).astype(np.float32), Ys, c["k"], 0.07, eps, G, ws=ws)
-        Ur, gr = _fwd_bwd_batched_c_abi(Xs, Ys, c["k"], 0.07, eps, G, ws=ws)[:2]
+        ws = fwd_bwd_batched_c_abi((Xs / scale).astype(np.float32), Ys, c["k"], 0.07, eps, G)[2].ws
+        Ur, gr = fwd_bwd_batched_c_abi(Xs, Ys, c["k"], 0.07, eps, G, ws=ws)[:2]
         np.testing.assert_array_equal(Ur, Uf)
         np.testing.assert_array_equal(gr, gf)
 
@@ -1229,13 +738,13 @@ def test_batched_graphs_stay_independent_with_non_finite_and_large_features():
     bitwise what they are in a batch without them, and the call returns (no hang, no fault)."""
     from graphlearninglayer_amd.synth import seeded_gbar
     B = 8
-    Xs, Ys, c = _synth_batch("ns", B, seed0=81)
+    Xs, Ys, c = synth_batch("ns", B, seed0=81)
     G = np.stack([seeded_gbar(c["batch"], 10, 900 + g) for g in range(B)])
-    U0, g0 = _fwd_bwd_batched_c_abi(Xs, Ys, c["k"], 0.07, 1.0, G)[:2]
+    U0, g0 = fwd_bwd_batched_c_abi(Xs, Ys, c["k"], 0.07, 1.0, G)[:2]
     Xb = Xs.copy()
     Xb[2, 700, :] = np.nan
     Xb[5] *= 1e4
-    U1, g1 = _fwd_bwd_batched_c_abi(Xb, Ys, c["k"], 0.07, 1.0, G)[:2]
+    U1, g1 = fwd_bwd_batched_c_abi(Xb, Ys, c["k"], 0.07, 1.0, G)[:2]
     for g in (0, 1, 3, 4, 6, 7):
         np.testing.assert_array_equal(U1[g], U0[g])
         np.testing.assert_array_equal(g1[g], g0[g])
@@ -1251,57 +760,21 @@ def test_batched_bench_route_matches_oracle_every_graph():
     graph's own GPU kNN lists."""
     from graphlearninglayer_amd.synth import seeded_gbar
     B = 64
-    Xs, Ys, c = _synth_batch("ns", B, seed0=300)
+    Xs, Ys, c = synth_batch("ns", B, seed0=300)
     G = np.stack([seeded_gbar(c["batch"], 10, 700 + g) for g in range(B)])
-    U, gx, ws, prob = _fwd_bwd_batched_c_abi(Xs, Ys, c["k"], 0.07, 1.0, G)
+    U, gx, run = fwd_bwd_batched_c_abi(Xs, Ys, c["k"], 0.07, 1.0, G)
     assert np.isfinite(U).all() and np.isfinite(gx).all()
     # the oracle is fed the kNN lists the batched launch wrote (each graph's workspace block),
     # and those lists are the exact float64 kNN
-    inds = _batched_knn_lists(ws, prob, B)
+    inds = batched_knn_lists(run)
     worst_u = worst_g = 0.0
     for g in range(B):
         ind = inds[g]
-        assert _exact_knn_rows(Xs[g], ind, c["k"]) == [], g
+        assert exact_knn_rows(Xs[g], ind, c["k"]) == [], g
         Uo, st = O.forward(Xs[g], Ys[g], tau=0.07, epsilon=1.0, K=c["k"], knn=(ind, None))
         worst_u = max(worst_u, O.rel_err(U[g], Uo))
         worst_g = max(worst_g, O.rel_err(gx[g], O.backward(st, G[g])))
     assert worst_u <= TOL and worst_g <= TOL, (worst_u, worst_g)
-
-
-@pytest.mark.parametrize("cfg,eps", [("ns", 1.0), ("ns", "auto"), ("fullysup", 1.0),
-                                     ("stress", 1.0), ("stress", "auto")])
-def test_chunked_grad_matches_row_kernel_bitwise(cfg, eps):
-    """The feature-chunked gradient kernel (grad.hip grad_chunk_kernel: features split over the
-    XCDs; automatic at stress, forced here elsewhere) sums every element in the same edge order as
-    the whole-row kernel: bitwise equal, and within the parity bar of the oracle
-    (GLL.py:111-159)."""
-    from graphlearninglayer_amd import _lib
-    from graphlearninglayer_amd.synth import CONFIGS, one_hot, seeded_gbar, synth
-    c = CONFIGS[cfg]
-    X, lab = synth(c["base"], c["batch"], c["d"], r=c["r"], seed=6)
-    Y = one_hot(lab[: c["base"]])
-    g = seeded_gbar(c["batch"], 10, 3)
-    Uc, gc, ran_c = _fwd_bwd_c_abi(X, Y, c["k"], 0.07, eps, g, flags=_lib.FLAG_GRAD_CHUNK,
-                                   counts=True)
-    Ur, gr, ran_r = _fwd_bwd_c_abi(X, Y, c["k"], 0.07, eps, g, flags=_lib.FLAG_GRAD_ROWS,
-                                   counts=True)
-    # the two sides ran different kernels: the edge pass + grad_chunk_kernel against the whole-row
-    # form (grad_spmm_kernel, or at NS with fixed eps the fused backward's gradient role)
-    from tests import grad_ref
-    shape = (c["base"] + c["batch"], c["d"], c["base"], 10, c["k"], 1, eps == "auto", True)
-    want_c = grad_ref.route(*shape, _lib.FLAG_GRAD_CHUNK)
-    want_r = grad_ref.route(*shape, _lib.FLAG_GRAD_ROWS)
-    assert want_c.family == "chunk" and want_r.family == (
-        "fused" if (cfg, eps) == ("ns", 1.0) else "spmm")
-    assert ran_c.counts == want_c.counts == (1, 1, 0, 1), ran_c
-    assert ran_r.counts == want_r.counts, ran_r
-    np.testing.assert_array_equal(Uc, Ur)
-    np.testing.assert_array_equal(gc, gr)
-    if cfg == "stress":   # the chunked kernel's automatic case; the oracle check runs elsewhere
-        return
-    ind = _gpu_knn(X, c["k"], eps)["knn_idx"].cpu().numpy().astype(np.int64)
-    Uo, st = O.forward(X, Y, tau=0.07, epsilon=eps, K=c["k"], knn=(ind, None))
-    assert O.rel_err(gc, O.backward(st, g)) <= TOL
 
 
 @pytest.mark.parametrize("d", [100, 37, 256])
@@ -1316,129 +789,25 @@ def test_presplit_gram_matches_inline_split(d):
     base, m, k = 1000, 3037, 10   # 32 128-row tiles a side: 528 tiles, the 128-tile path
     X, lab = synth(base, m, d, r=1.0, seed=8)
     Y = one_hot(lab[:base])
-    Ui, iti, nci = _forward_c_abi(X, Y, k, 0.07, "auto", flags=_lib.FLAG_GRAM_INLINE)
+    Ui, iti, nci = forward_c_abi(X, Y, k, 0.07, "auto", flags=_lib.FLAG_GRAM_INLINE)
     assert nci == 0
-    ind = _gpu_knn(X, k, "auto")["knn_idx"].cpu().numpy()
-    assert _exact_knn_rows(X, ind, k) == []
+    ind = gpu_knn(X, k, "auto")["knn_idx"].cpu().numpy()
+    assert exact_knn_rows(X, ind, k) == []
     if d > 128:
-        Up, itp, ncp = _forward_c_abi(X, Y, k, 0.07, "auto")
+        Up, itp, ncp = forward_c_abi(X, Y, k, 0.07, "auto")
         assert ncp == 0
         np.testing.assert_array_equal(Up, Ui)
         return
     # single graphs with d <= 128 take the inline kernel (gram.hip launch_gram); batches keep the
     # pre-split one: a batch of two (this graph and a second) against the single calls, at the
     # batched-parity bar (the batched launch runs a different CG configuration)
-    GLL = _gll()
     X2, lab2 = synth(base, m, d, r=1.0, seed=9)
     Xb = torch.from_numpy(np.stack([X, X2])).cuda()
     Yb = torch.from_numpy(np.stack([Y, one_hot(lab2[:base])])).cuda()
     Ub = GLL.LaplaceLearningSparseHard.apply(Xb, Yb, 0.07, "auto", k).cpu().numpy()
     assert O.rel_err(Ub[0], Ui) <= 1e-5
-    U2, _, _ = _forward_c_abi(X2, one_hot(lab2[:base]), k, 0.07, "auto")
+    U2, _, _ = forward_c_abi(X2, one_hot(lab2[:base]), k, 0.07, "auto")
     assert O.rel_err(Ub[1], U2) <= 1e-5
-
-
-def _fwd_bwds_c_abi(X, Y, k, tau, eps, gbar, flags=0, backward_calls=1, counts=False):
-    """gll_forward then `backward_calls` x gll_backward on ONE workspace through ctypes, every
-    output NaN-filled before its call: (U, [grad_X], status words) and, with `counts`, the
-    launches of each backward (tests/launch_counts.py)."""
-    import ctypes as ct
-    from graphlearninglayer_amd import _lib
-    GLL = _gll()
-    n, d = X.shape
-    base, C = Y.shape
-    prob = GLL.make_problem(n, d, base, C, k, tau, eps, flags=flags)
-    lib = _lib.lib()
-    ws = torch.empty(lib.gll_workspace_bytes(ct.byref(prob)), dtype=torch.uint8, device="cuda")
-    U = _nan(n - base, C, dtype=torch.float64)
-    Xd = torch.from_numpy(np.ascontiguousarray(X)).cuda()
-    Yd = torch.from_numpy(np.ascontiguousarray(Y)).cuda()
-    Gd = torch.from_numpy(np.ascontiguousarray(gbar)).cuda()
-    s = torch.cuda.current_stream().cuda_stream
-    _lib.check(lib.gll_forward(ct.byref(prob), Xd.data_ptr(), Yd.data_ptr(), _lib.GLL_DT_F32,
-                               ws.data_ptr(), U.data_ptr(), s), "gll_forward")
-    import contextlib
-    from tests.launch_counts import counted
-    grads, launches = [], []
-    for _ in range(backward_calls):
-        gx = _nan(n, d, dtype=torch.float32)
-        with (counted() if counts else contextlib.nullcontext()) as got:
-            _lib.check(lib.gll_backward(ct.byref(prob), Xd.data_ptr(), None, 0, ws.data_ptr(),
-                                        Gd.data_ptr(), _lib.GLL_DT_F64, gx.data_ptr(), s),
-                       "gll_backward")
-        grads.append(gx.cpu().numpy())
-        launches.append(got.counts if counts else None)
-    st = ws[: 4 * _lib.ST_NWORDS].view(torch.int32).cpu().tolist()
-    if counts:
-        return U.cpu().numpy(), grads, st, launches
-    return U.cpu().numpy(), grads, st
-
-
-@pytest.mark.parametrize("cfg", ["plumbing", "ns", "wide_base"])
-def test_fused_backward_equals_two_launches_bitwise(cfg):
-    """The fused backward (adjoint CG + feature gradient in one launch, fused_bwd.hip
-    cg_grad_fused_kernel: single small graphs, fixed eps) against the same two kernels as two
-    launches (GLL_FLAG_BWD_UNFUSED): bitwise equal, and equal again on a second backward over
-    the same workspace (the hand-off counters re-arm); against the float64 oracle at 1e-4.
-    The gradient waves take the rows in class order (round 6); `wide_base`
-    (1,400 labeled + 500 unlabeled rows at d = 128) sorts 30 64-row chunks in 248 workgroups,
-    the most the 256 CUs hold co-resident (at 3,500 + 500 rows the launch needs 510, the fused
-    kernel declines and both sides of this comparison would be the two-launch path).  Which
-    side ran which kernels is asserted from the bracketed launches."""
-    from graphlearninglayer_amd import _lib
-    from graphlearninglayer_amd.synth import CONFIGS, one_hot, seeded_gbar, synth
-    c = CONFIGS[cfg] if cfg in CONFIGS else dict(base=1400, batch=500, d=128, k=10, r=1.0)
-    X, lab = synth(c["base"], c["batch"], c["d"], r=c["r"], seed=6)
-    Y = one_hot(lab[: c["base"]])
-    g = seeded_gbar(c["batch"], 10, 17)
-    Uf, gf, stf, ran_f = _fwd_bwds_c_abi(X, Y, c["k"], 0.07, 1.0, g, backward_calls=3,
-                                         counts=True)
-    Uu, gu, stu, ran_u = _fwd_bwds_c_abi(X, Y, c["k"], 0.07, 1.0, g, flags=_lib.FLAG_BWD_UNFUSED,
-                                         counts=True)
-    # (edge pass, gradient, fused backward, CG) launches: one fused launch per backward against
-    # a CG and a gradient launch
-    assert ran_f == [(0, 0, 1, 0)] * 3, ran_f
-    assert ran_u == [(0, 1, 0, 1)], ran_u
-    np.testing.assert_array_equal(Uf, Uu)
-    for gx in gf:
-        np.testing.assert_array_equal(gx, gu[0])
-    assert stf[_lib.ST_SOLVE_FAILED] == 0 and stf[_lib.ST_BWD_NONCONV] == 0
-    assert stf[_lib.ST_BWD_ITERS] == stu[_lib.ST_BWD_ITERS] > 0
-    ind = _gpu_knn(X, c["k"], 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
-    Uo, st = O.forward(X, Y, tau=0.07, epsilon=1.0, K=c["k"], knn=(ind, None))
-    assert O.rel_err(gf[0], O.backward(st, g)) <= TOL
-
-
-@pytest.mark.parametrize("live", [(3,), (0, 9), (4, 5, 6)])
-def test_fused_backward_handoff_with_uneven_column_solves(live):
-    """The fused backward's hand-off with column solves of very different
-    lengths: dL/dU is zero in all but the `live` columns, so those columns' adjoint solves run
-    their iterations while the zero columns finish at once and raise the counter first; the 125
-    gradient workgroups (one per CU, every XCD) poll while a single column is still iterating.
-    Bitwise equal to the two-launch backward, on three backwards over one workspace (re-arm), and
-    to the float64 oracle at 1e-4."""
-    from graphlearninglayer_amd import _lib
-    from graphlearninglayer_amd.synth import CONFIGS, one_hot, seeded_gbar, synth
-    c = CONFIGS["ns"]
-    X, lab = synth(c["base"], c["batch"], c["d"], r=c["r"], seed=21)
-    Y = one_hot(lab[: c["base"]])
-    g = np.zeros((c["batch"], 10))
-    full = seeded_gbar(c["batch"], 10, 23)
-    for q, col in enumerate(live):
-        g[:, col] = full[:, col] * 10.0 ** (3 * q)   # scales 1, 1e3, 1e6
-    Uf, gf, stf, ran_f = _fwd_bwds_c_abi(X, Y, c["k"], 0.07, 1.0, g, backward_calls=3,
-                                         counts=True)
-    Uu, gu, stu, ran_u = _fwd_bwds_c_abi(X, Y, c["k"], 0.07, 1.0, g, flags=_lib.FLAG_BWD_UNFUSED,
-                                         counts=True)
-    assert ran_f == [(0, 0, 1, 0)] * 3, ran_f      # the fused kernel, every backward
-    assert ran_u == [(0, 1, 0, 1)], ran_u          # a CG launch and a gradient launch
-    for gx in gf:
-        np.testing.assert_array_equal(gx, gu[0])
-    assert stf[_lib.ST_SOLVE_FAILED] == 0 and stf[_lib.ST_BWD_NONCONV] == 0
-    assert stf[_lib.ST_BWD_ITERS] == stu[_lib.ST_BWD_ITERS] > 0
-    ind = _gpu_knn(X, c["k"], 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
-    Uo, st = O.forward(X, Y, tau=0.07, epsilon=1.0, K=c["k"], knn=(ind, None))
-    assert O.rel_err(gf[0], O.backward(st, g)) <= TOL
 
 
 @pytest.mark.parametrize("cfg,B,n_extra,d", [("ns", 3, 0, None), ("fullysup", 2, 0, None),
@@ -1451,7 +820,6 @@ def test_gram_256_tiles_match_128_tiles(cfg, B, n_extra, d, monkeypatch):
     and 1,037): 260 256-tiles on a 256-CU device, whose short last round runs as 64-subtiles (the
     launch's tail); B = 64: 640 256-tiles, a third round of 256-tiles."""
     from graphlearninglayer_amd.synth import CONFIGS, one_hot, seeded_gbar, synth
-    GLL = _gll()
     c = dict(CONFIGS[cfg])
     if d is not None:
         c["d"] = d
@@ -1464,16 +832,13 @@ def test_gram_256_tiles_match_128_tiles(cfg, B, n_extra, d, monkeypatch):
                                    for g in range(B)])).cuda()
     from graphlearninglayer_amd import _lib
     outs = []
-    try:
-        for tile in (128, 256):
-            _lib.set_knob(_lib.KNOB_GRAM_TILE, tile)
+    for tile in (128, 256):
+        with A.knobs({_lib.KNOB_GRAM_TILE: tile}):
             Xb = torch.from_numpy(np.stack(Xs)).cuda().requires_grad_(True)
             U = GLL.LaplaceLearningSparseHard.apply(Xb, torch.from_numpy(np.stack(Ys)).cuda(),
                                                     0.07, 1.0, c["k"])
             U.backward(G)
             outs.append((U.detach().cpu().numpy(), Xb.grad.cpu().numpy()))
-    finally:
-        _lib.set_knob(_lib.KNOB_GRAM_TILE, 0)
     np.testing.assert_array_equal(outs[0][0], outs[1][0])
     np.testing.assert_array_equal(outs[0][1], outs[1][1])
 
@@ -1489,14 +854,11 @@ def test_gram_tail_changes_no_result():
     c = CONFIGS["stress"]
     X, _ = synth(c["base"], c["batch"], c["d"], r=c["r"], seed=5)
     outs = []
-    try:
-        for tail in (0, 1, 2):
-            _lib.set_knob(_lib.KNOB_GRAM_TAIL, tail)
-            g = _gpu_knn(X, c["k"], "auto")
+    for tail in (0, 1, 2):
+        with A.knobs({_lib.KNOB_GRAM_TAIL: tail}):
+            g = gpu_knn(X, c["k"], "auto")
             outs.append({key: g[key].cpu().numpy() for key in ("knn_idx", "knn_d2", "eps")})
             assert int(g["status"][_lib.ST_KNN_RESCAN].item()) == 0, tail
-    finally:
-        _lib.set_knob(_lib.KNOB_GRAM_TAIL, 0)
     for key in outs[0]:
         np.testing.assert_array_equal(outs[1][key], outs[0][key])
         np.testing.assert_array_equal(outs[2][key], outs[0][key])
@@ -1514,27 +876,8 @@ def test_locality_order_changes_no_result(eps):
     X, lab = synth(c["base"], c["batch"], c["d"], r=c["r"], seed=5)
     Y = one_hot(lab[: c["base"]])
     g = seeded_gbar(c["batch"], 10, 6)
-    U0, g0 = _fwd_bwd_c_abi(X, Y, c["k"], 0.07, eps, g)
-    U1, g1 = _fwd_bwd_c_abi(X, Y, c["k"], 0.07, eps, g, flags=_lib.FLAG_ROW_ORDER_OFF)
-    np.testing.assert_array_equal(U0, U1)
-    np.testing.assert_array_equal(g0, g1)
-
-
-def test_backward_never_reads_an_order_its_forward_did_not_write():
-    """gll_backward takes its own gll_problem, so its flags may differ from the forward's: a
-    forward with GLL_FLAG_ROW_ORDER_OFF writes no locality order, and the backward then must not
-    gather rows through the workspace's stale perm (here all zeros: every position would map to
-    row 0, leaving the other rows of grad_X unwritten).  grad_X equals the row-order result
-    bitwise (GLL.py:146-159)."""
-    from graphlearninglayer_amd import _lib
-    from graphlearninglayer_amd.synth import CONFIGS, one_hot, seeded_gbar, synth
-    c = CONFIGS["stress"]
-    X, lab = synth(c["base"], c["batch"], c["d"], r=c["r"], seed=5)
-    Y = one_hot(lab[: c["base"]])
-    g = seeded_gbar(c["batch"], 10, 6)
-    off = _lib.FLAG_ROW_ORDER_OFF
-    U0, g0 = _fwd_bwd_c_abi(X, Y, c["k"], 0.07, 1.0, g, flags=off)
-    U1, g1 = _fwd_bwd_c_abi(X, Y, c["k"], 0.07, 1.0, g, flags=off, bwd_flags=0, ws_fill=0)
+    U0, g0 = fwd_bwd_c_abi(X, Y, c["k"], 0.07, eps, g)
+    U1, g1 = fwd_bwd_c_abi(X, Y, c["k"], 0.07, eps, g, flags=_lib.FLAG_ROW_ORDER_OFF)
     np.testing.assert_array_equal(U0, U1)
     np.testing.assert_array_equal(g0, g1)
 
@@ -1550,16 +893,13 @@ def test_select_forms_agree_bitwise(k, d):
     from graphlearninglayer_amd.synth import synth
     X, _ = synth(1000, 2000, d, r=1.0, seed=71)
     outs = []
-    try:
-        for form in (1, 2):
-            _lib.set_knob(_lib.KNOB_SEL_FORM, form)
-            g = _gpu_knn(X, k, "auto")
+    for form in (1, 2):
+        with A.knobs({_lib.KNOB_SEL_FORM: form}):
+            g = gpu_knn(X, k, "auto")
             outs.append({key: g[key].cpu().numpy() for key in ("knn_idx", "knn_d2", "eps")})
-    finally:
-        _lib.set_knob(_lib.KNOB_SEL_FORM, 0)
     for key in outs[0]:
         np.testing.assert_array_equal(outs[0][key], outs[1][key])
-    assert _exact_knn_rows(X, outs[0]["knn_idx"], k) == []
+    assert exact_knn_rows(X, outs[0]["knn_idx"], k) == []
 
 
 # ----------------------------------------------------------------------------------------
@@ -1582,9 +922,9 @@ def test_class_counts_match_oracle(C, eps):
     """NS shape (500 + 500 x 512, k = 10), C classes: U and grad_X through apply against the
     float64 oracle on the GPU's own kNN lists (GLL.py:14-177)."""
     X, Y, g = _classes_case(C, eps, seed=40 + C)
-    U, gx = _run(X, Y, 0.07, eps, 10, g)
+    U, gx = run_layer(X, Y, 0.07, eps, 10, g)
     assert U.shape == (500, C)
-    ind = _gpu_knn(X, 10, eps)["knn_idx"].cpu().numpy().astype(np.int64)
+    ind = gpu_knn(X, 10, eps)["knn_idx"].cpu().numpy().astype(np.int64)
     Uo, st = O.forward(X, Y, tau=0.07, epsilon=eps, K=10, knn=(ind, None))
     assert O.rel_err(U, Uo) <= TOL
     assert O.rel_err(gx, O.backward(st, g)) <= TOL
@@ -1597,7 +937,6 @@ def test_class_counts_batched_match_oracle(C, eps, shape):
     with the per-edge coefficient pass (edge_coef_kernel<4>/<-16>), NS batches the whole-row
     gradient's generic-C form; every graph against the oracle."""
     from graphlearninglayer_amd.synth import CONFIGS, one_hot, seeded_gbar, synth
-    GLL = _gll()
     c = CONFIGS[shape]
     B = 2
     Xs, Ys, Gs = [], [], []
@@ -1611,7 +950,7 @@ def test_class_counts_batched_match_oracle(C, eps, shape):
                                              c["k"])
     Ub.backward(torch.from_numpy(np.stack(Gs)).cuda())
     for g_ in range(B):
-        ind = _gpu_knn(Xs[g_], c["k"], eps)["knn_idx"].cpu().numpy().astype(np.int64)
+        ind = gpu_knn(Xs[g_], c["k"], eps)["knn_idx"].cpu().numpy().astype(np.int64)
         Uo, st = O.forward(Xs[g_], Ys[g_], tau=0.07, epsilon=eps, K=c["k"], knn=(ind, None))
         assert O.rel_err(Ub[g_].detach().cpu().numpy(), Uo) <= TOL
         assert O.rel_err(Xb.grad[g_].cpu().numpy(), O.backward(st, Gs[g_])) <= TOL
@@ -1621,56 +960,11 @@ def test_class_count_past_the_grid_cg_large_single_graph():
     """A single graph with m > 2048 and C = 17: the whole-GPU CG holds C <= 16, so the solves
     take the per-column kernels; U and grad_X against the oracle."""
     X, Y, g = _classes_case(17, 1.0, seed=81, base=500, batch=2500, d=64, k=10)
-    U, gx = _run(X, Y, 0.07, 1.0, 10, g)
-    ind = _gpu_knn(X, 10, 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
+    U, gx = run_layer(X, Y, 0.07, 1.0, 10, g)
+    ind = gpu_knn(X, 10, 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
     Uo, st = O.forward(X, Y, tau=0.07, epsilon=1.0, K=10, knn=(ind, None))
     assert O.rel_err(U, Uo) <= TOL
     assert O.rel_err(gx, O.backward(st, g)) <= TOL
-
-
-@pytest.mark.parametrize("C,nu", [(3, 2750), (17, 2750)])
-def test_utils_laplace_auto_class_count(C, nu):
-    """utils.laplace with n_classes = 'auto' on labels of C classes (utils.py:556-568,570-593):
-    the one-hot width follows the labels, the CSR solve (gll_cg_csr: the whole-GPU CG for
-    C <= 16, per-column kernels past it) against the oracle."""
-    from graphlearninglayer_amd import utils as U_
-    from graphlearninglayer_amd.synth import synth
-    X, labels = synth(250, nu, 64, C=C, r=1.0, seed=90 + C)
-    train = labels[:250]
-    U = U_.laplace(X, train, knn_num=20, epsilon=1.0, tau=1e-8)
-    assert U.shape == (nu, C)
-    ind = _gpu_knn(X, 20, 1.0)["knn_idx"].cpu().numpy().astype(np.int64)
-    Uo = O.laplace(X, train, knn_num=20, epsilon=1.0, tau=1e-8, knn=(ind, None))
-    assert Uo.shape == (nu, C)
-    assert O.rel_err(U, Uo) <= TOL
-
-
-@pytest.mark.parametrize("m,k,eps", [(333, 10, 1.0), (500, 10, "auto"), (449, 11, 1.0)])
-def test_batched_two_row_cg_ragged_and_hub_rows_match_oracle(m, k, eps):
-    """The batched 256 x 2 CG (B x C > 256 column workgroups, 256 < m <= 512; solve.hip
-    cg_dispatch) with ragged row counts (m = 333, 449: dead threads in the last waves), and in
-    every third graph a hub -- 40 rows placed around one U row, whose U block then passes the 24
-    register slots (its tail comes from the LDS overflow) -- every such graph's U and grad_X
-    against the float64 oracle on its own kNN lists (GLL.py:53,93)."""
-    from graphlearninglayer_amd.synth import one_hot, seeded_gbar, synth
-    B, base, d = 32, 200, 64
-    Xs, Ys, Gs = [], [], []
-    rng = np.random.default_rng(7)
-    for g in range(B):
-        X, lab = synth(base, m, d, r=1.0, seed=500 + g)
-        if g % 3 == 0:   # a hub: rows 260..299 around row 250 (all U rows)
-            X[260:300] = X[250] + 0.02 * rng.standard_normal((40, d)).astype(np.float32)
-            X[260:300] /= np.linalg.norm(X[260:300], axis=1, keepdims=True)
-        Xs.append(X)
-        Ys.append(one_hot(lab[:base]))
-        Gs.append(seeded_gbar(m, 10, 600 + g))
-    Xs, Ys, G = np.stack(Xs), np.stack(Ys), np.stack(Gs)
-    U, gx, ws, prob = _fwd_bwd_batched_c_abi(Xs, Ys, k, 0.07, eps, G)
-    inds = _batched_knn_lists(ws, prob, B)
-    for g in range(0, B, 3):
-        Uo, st = O.forward(Xs[g], Ys[g], tau=0.07, epsilon=eps, K=k, knn=(inds[g], None))
-        assert O.rel_err(U[g], Uo) <= TOL, g
-        assert O.rel_err(gx[g], O.backward(st, G[g])) <= TOL, g
 
 
 # ----------------------------------------------------------------------------------------
@@ -1688,11 +982,11 @@ def test_wide_k_exact_knn_and_oracle(k, eps):
     X, lab = synth(c["base"], c["batch"], c["d"], r=c["r"], seed=31)
     Y = one_hot(lab[: c["base"]])
     g = seeded_gbar(c["batch"], 10, 32)
-    ind = _gpu_knn(X, k, eps)["knn_idx"].cpu().numpy()
+    ind = gpu_knn(X, k, eps)["knn_idx"].cpu().numpy()
     assert ind.shape == (c["base"] + c["batch"], k)
     assert (ind[:, 0] == np.arange(ind.shape[0])).all()
-    assert _exact_knn_rows(X, ind, k) == []
-    U, gx = _run(X, Y, 0.07, eps, k, g)
+    assert exact_knn_rows(X, ind, k) == []
+    U, gx = run_layer(X, Y, 0.07, eps, k, g)
     Uo, st = O.forward(X, Y, 0.07, eps, k, knn=(ind.astype(np.int64), None))
     assert O.rel_err(U, Uo) <= TOL
     assert O.rel_err(gx, O.backward(st, g)) <= TOL
@@ -1705,26 +999,25 @@ def test_wide_k_batched_and_rescan():
     exact float64 kNN and the oracle's solve."""
     from graphlearninglayer_amd import _lib
     from graphlearninglayer_amd.synth import one_hot, seeded_gbar, synth
-    GLL = _gll()
     k, B = 64, 3
-    Xs, Ys, c = _synth_batch("ns", B, seed0=41)
+    Xs, Ys, c = synth_batch("ns", B, seed0=41)
     G = np.stack([seeded_gbar(c["batch"], 10, 42 + g) for g in range(B)])
     Xb = torch.from_numpy(Xs).cuda().requires_grad_(True)
     Ub = GLL.LaplaceLearningSparseHard.apply(Xb, torch.from_numpy(Ys).cuda(), 0.07, 1.0, k)
     Ub.backward(torch.from_numpy(G).cuda())
     for g in range(B):
-        U1, gx1 = _run(Xs[g], Ys[g], 0.07, 1.0, k, G[g])
+        U1, gx1 = run_layer(Xs[g], Ys[g], 0.07, 1.0, k, G[g])
         assert O.rel_err(Ub[g].detach().cpu().numpy(), U1) <= 1e-5
         assert O.rel_err(Xb.grad[g].cpu().numpy(), gx1) <= 1e-5
     X, lab = synth(100, 400, 64, r=1.0, seed=23)
     X[0] = 300.0 / np.sqrt(64)
-    gg = _gpu_knn(X, 80, "auto")
+    gg = gpu_knn(X, 80, "auto")
     ind = gg["knn_idx"].cpu().numpy()
     assert int(gg["status"][_lib.ST_KNN_RESCAN].item()) > 100
-    assert _exact_knn_rows(X, ind, 80) == []
+    assert exact_knn_rows(X, ind, 80) == []
     Y = one_hot(lab[:100])
     gb = seeded_gbar(400, 10, 5)
-    U, grad = _run(X, Y, 0.07, "auto", 80, gb)
+    U, grad = run_layer(X, Y, 0.07, "auto", 80, gb)
     Uo, st = O.forward(X, Y, 0.07, "auto", 80, knn=(ind.astype(np.int64), None))
     assert O.rel_err(U, Uo) < TOL
     assert O.rel_err(grad, O.backward(st, gb)) < TOL
@@ -1745,11 +1038,11 @@ def test_wide_k_ties_past_the_candidate_slots(k):
     lab = np.arange(n) % 10
     Y = np.eye(10, dtype=np.float32)[lab[:base]]
     gb = rng.standard_normal((n - base, 10))
-    g = _gpu_knn(X, k, 1.0)
+    g = gpu_knn(X, k, 1.0)
     ind = g["knn_idx"].cpu().numpy()
     assert int(g["status"][_lib.ST_KNN_MERGE].item()) > 0
     assert O.knn_set_mismatch(X, ind, k) == []
-    U, grad = _run(X, Y, 0.07, 1.0, k, gb)
+    U, grad = run_layer(X, Y, 0.07, 1.0, k, gb)
     Uo, st = O.forward(X, Y, 0.07, 1.0, k, knn=(ind.astype(np.int64), None))
     assert O.rel_err(U, Uo) < TOL
     assert O.rel_err(grad, O.backward(st, gb)) < TOL
@@ -1764,35 +1057,14 @@ def test_wide_k_row_panels_match_whole_matrix(k, eps):
     X, lab = synth(300, 2200, 64, C=10, r=1.0, seed=61)
     Y = one_hot(lab[:300])
     g = seeded_gbar(2200, 10, 62)
-    U0, gr0 = _fwd_bwd_c_abi(X, Y, k, 0.07, eps, g)
-    U1, gr1 = _fwd_bwd_c_abi(X, Y, k, 0.07, eps, g, flags=_lib.FLAG_KNN_PANEL)
+    U0, gr0 = fwd_bwd_c_abi(X, Y, k, 0.07, eps, g)
+    U1, gr1 = fwd_bwd_c_abi(X, Y, k, 0.07, eps, g, flags=_lib.FLAG_KNN_PANEL)
     np.testing.assert_array_equal(U0, U1)
     np.testing.assert_array_equal(gr0, gr1)
-    ind = _gpu_knn(X, k, eps)["knn_idx"].cpu().numpy().astype(np.int64)
+    ind = gpu_knn(X, k, eps)["knn_idx"].cpu().numpy().astype(np.int64)
     Uo, st = O.forward(X, Y, 0.07, eps, k, knn=(ind, None))
     assert O.rel_err(U1, Uo) <= TOL
     assert O.rel_err(gr1, O.backward(st, g)) <= TOL
-
-
-@pytest.mark.parametrize("knn_num", [64, 100, 200])
-def test_utils_laplace_wide_knn_num(knn_num):
-    """utils.laplace with knn_num = 64 / 100 (utils.py:574) on 250 + 4,000 points: exact kNN
-    on sampled rows and the oracle's solution."""
-    from graphlearninglayer_amd import utils as U_
-    from graphlearninglayer_amd.synth import synth
-    X, labels = synth(250, 4000, 64, C=10, r=1.0, seed=50 + knn_num)
-    train = labels[:250]
-    U = U_.laplace(X, train, knn_num=knn_num, epsilon=1.0, tau=1e-8)
-    ind = _gpu_knn(X, knn_num, 1.0)["knn_idx"].cpu().numpy()
-    Uo = O.laplace(X, train, knn_num=knn_num, epsilon=1.0, tau=1e-8,
-                   knn=(ind.astype(np.int64), None))
-    assert O.rel_err(U, Uo) <= TOL
-    rng = np.random.default_rng(1)
-    X64 = X.astype(np.float64)
-    for i in rng.choice(X.shape[0], 48, replace=False):
-        d2 = np.sum((X64 - X64[i]) ** 2, axis=1)
-        order = np.argsort(d2, kind="stable")
-        assert set(ind[i].tolist()) == set(order[:knn_num].tolist()), i
 
 
 def _select_point_id(pt):
@@ -1822,51 +1094,29 @@ def test_every_select_variant_is_exact(pt):
     storage among them): every graph's lists, distances and eps, read from its workspace block,
     are bitwise those of the single-graph call on that graph's rows under GLL_FLAG_D2_F32, and
     the float64 sets."""
-    import ctypes as ct
     from graphlearninglayer_amd import _lib
     from tests import select_points as SP
     n, d, k, B, panel, form = pt
     Xs = SP.features(n, d, B)
-    GLL = _gll()
     if B == 1:
-        try:
-            _lib.set_knob(_lib.KNOB_SEL_FORM, form)
+        with A.knobs({_lib.KNOB_SEL_FORM: form}):
             g = GLL.device_graph(torch.from_numpy(Xs[0]).cuda(), k, "auto",
                                  flags=_lib.FLAG_KNN_PANEL if panel else 0)
             ind, d2 = g["knn_idx"].cpu().numpy(), g["knn_d2"].cpu().numpy()
-        finally:
-            _lib.set_knob(_lib.KNOB_SEL_FORM, 0)
         _check_exact_lists(Xs[0], ind, d2, k)
         return
     base, C = 8, 2
-    prob = GLL.make_problem(n, d, base, C, k, 0.07, "auto")
-    prob.max_iter = 2   # the solve is not what this test reads
-    lib = _lib.lib()
-    wb = lib.gll_workspace_bytes(ct.byref(prob))
-    ws = torch.empty(B * wb, dtype=torch.uint8, device="cuda")
-    U = torch.empty(B, n - base, C, dtype=torch.float64, device="cuda")
-    Xd = torch.from_numpy(np.stack(Xs)).cuda()
-    Yd = torch.zeros(B, base, C, dtype=torch.float32, device="cuda")
-    Yd[:, :, 0] = 1.0
-    _lib.check(lib.gll_forward_batched(ct.byref(prob), B, Xd.data_ptr(), Yd.data_ptr(),
-                                       _lib.GLL_DT_F32, ws.data_ptr(), U.data_ptr(),
-                                       torch.cuda.current_stream().cuda_stream),
-               "gll_forward_batched")
-    torch.cuda.synchronize()
-    K = prob.K
+    Y = np.zeros((B, base, C), dtype=np.float32)
+    Y[:, :, 0] = 1.0
+    run = A.Run(np.stack(Xs), Y, k, 0.07, "auto", max_iter=2)   # the solve is not read here
+    run.forward()
+    K = run.problem().K
     for g in range(B):
-        view = _lib.View()
-        _lib.check(lib.gll_workspace_view(ct.byref(prob), ws.data_ptr() + g * wb, ct.byref(view)),
-                   "gll_workspace_view")
-
-        def arr(ptr, count, dtype):
-            off = ptr - ws.data_ptr()
-            return ws[off: off + 4 * count].view(dtype).cpu().numpy()
-
-        ind = arr(view.knn_idx, n * K, torch.int32).reshape(n, K)
-        d2 = arr(view.knn_d2, n * K, torch.float32).reshape(n, K)
-        eps = arr(view.eps, n, torch.float32)
-        one = GLL.device_graph(Xd[g], k, "auto", flags=_lib.FLAG_D2_F32)
+        view = run.view(g)
+        ind = run.array(view.knn_idx, n * K, np.int32, g).reshape(n, K)
+        d2 = run.array(view.knn_d2, n * K, np.float32, g).reshape(n, K)
+        eps = run.array(view.eps, n, np.float32, g)
+        one = GLL.device_graph(run.X[g], k, "auto", flags=_lib.FLAG_D2_F32)
         np.testing.assert_array_equal(ind, one["knn_idx"].cpu().numpy())
         np.testing.assert_array_equal(d2, one["knn_d2"].cpu().numpy())
         np.testing.assert_array_equal(eps, one["eps"].cpu().numpy())

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import abi as A
 from tests import query_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -26,17 +27,11 @@ def _G():
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    _L().lib()  # fail loudly when the HIP library is missing
-
-
-def _dev(a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()   # a copy: the cases are read-only
+    A.need_gpu()
 
 
 def _query(Xq, Xdb, k, flags=0):
-    idx, d2, st = _G().knn_query(_dev(Xq), _dev(Xdb), k, flags=flags, return_status=True)
+    idx, d2, st = _G().knn_query(A.dev(Xq), A.dev(Xdb), k, flags=flags, return_status=True)
     return idx.cpu().numpy(), d2.cpu().numpy(), st.cpu().numpy()
 
 
@@ -114,7 +109,7 @@ def test_row_of_a_call_equals_the_call_on_that_row_and_runs_repeat():
 @pytest.mark.parametrize("name", ["eval_like", "ragged"])
 def test_misaligned_storage_gives_the_aligned_bits(name):
     Xq, Xdb, k, *_ = R.case(name)
-    aq, adb = _dev(Xq), _dev(Xdb)
+    aq, adb = A.dev(Xq), A.dev(Xdb)
     assert aq.data_ptr() % 16 == 0 and adb.data_ptr() % 16 == 0
     ref = _raw_query(aq, adb, k)
 
@@ -134,7 +129,7 @@ def test_self_query_matches_the_graph_build():
     n, d, K = 500, 32, 10
     X = np.random.default_rng(21).standard_normal((n, d)).astype(np.float32)
     assert R.boundary_gap(X, X, K).min() > R.tie_gap(d)
-    g = _G().device_graph(_dev(X), K)
+    g = _G().device_graph(A.dev(X), K)
     gi, gd = g["knn_idx"].cpu().numpy().astype(np.int64), g["knn_d2"].cpu().numpy().astype(np.float64)
     idx, d2, _ = _query(X, X, K)
     o, og = np.argsort(idx, axis=1), np.argsort(gi, axis=1)
@@ -182,8 +177,8 @@ def test_non_finite_features_keep_every_index_in_range():
 @pytest.mark.parametrize("name", list(R.EXT_CASES))
 def test_extend_within_the_derived_bound_and_every_label_equal(name):
     Xq, Xdb, P, k, epsilon, eps_db, Uq_ref, lab_ref, bound = R.ext_case(name)
-    Uq, lab, st = _G().extend(_dev(Xq), _dev(Xdb), _dev(P), k=k, epsilon=epsilon,
-                              eps_db=None if eps_db is None else _dev(eps_db), return_status=True)
+    Uq, lab, st = _G().extend(A.dev(Xq), A.dev(Xdb), A.dev(P), k=k, epsilon=epsilon,
+                              eps_db=None if eps_db is None else A.dev(eps_db), return_status=True)
     assert Uq.dtype == torch.float64 and lab.dtype == torch.int64
     err = np.abs(Uq.cpu().numpy() - Uq_ref).max()
     print(name, "max |Uq - ref|", err, "bound", bound)
@@ -194,12 +189,12 @@ def test_extend_within_the_derived_bound_and_every_label_equal(name):
 
 def test_extend_zero_weight_sum_is_nan_and_counted():
     Xq, Xdb, P, k, *_ = R.ext_case("fixed")
-    Uq, lab, st = _G().extend(_dev(Xq), _dev(Xdb), _dev(P), k=k, epsilon=1e-3, return_status=True)
+    Uq, lab, st = _G().extend(A.dev(Xq), A.dev(Xdb), A.dev(P), k=k, epsilon=1e-3, return_status=True)
     assert torch.isnan(Uq).all() and (lab == 0).all()
     assert st.cpu()[_L().QST_ZERO_SUM] == len(Xq)
-    Uq0, lab0 = _G().extend(_dev(Xq[:0]), _dev(Xdb), _dev(P), k=k, epsilon=1.0)
+    Uq0, lab0 = _G().extend(A.dev(Xq[:0]), A.dev(Xdb), A.dev(P), k=k, epsilon=1.0)
     assert Uq0.shape == (0, P.shape[1]) and lab0.shape == (0,)
-    i0, f0 = _G().knn_query(_dev(Xq[:0]), _dev(Xdb), 3)
+    i0, f0 = _G().knn_query(A.dev(Xq[:0]), A.dev(Xdb), 3)
     assert i0.shape == (0, 3) and i0.dtype == torch.int64 and f0.shape == (0, 3) and i0.is_cuda
 
 
@@ -221,7 +216,7 @@ def test_laplace_predict_is_extend_on_the_fit(epsilon):
     assert np.allclose(fit.P[base:].cpu().numpy(), U, rtol=0, atol=1e-6)
     assert (fit.P[:base].cpu().numpy() == np.eye(C, dtype=np.float32)[lab[:base]]).all()
     Uq, labels = utils.laplace_predict(fit, Xq, knn_num=kk)
-    Ue, le = _G().extend(_dev(Xq), fit.X, fit.P, k=kk, epsilon=epsilon, eps_db=fit.eps)
+    Ue, le = _G().extend(A.dev(Xq), fit.X, fit.P, k=kk, epsilon=epsilon, eps_db=fit.eps)
     assert Uq.cpu().numpy().tobytes() == Ue.cpu().numpy().tobytes() and (labels == le).all()
     assert (labels.cpu().numpy() == np.arange(40) % C).mean() > 0.9
     acc = utils.gl_accuracy_inductive(X[:base], lab[:base], Xq, np.arange(40) % C,
@@ -233,7 +228,7 @@ def test_launches_per_call():
     """three launches a panel (norms, Gram, select), one for the extension."""
     lib = _L().lib()
     Xq, Xdb, k, *_ = R.case("offset100")     # 70 rows: one panel, or two of 64
-    aq, adb = _dev(Xq), _dev(Xdb)
+    aq, adb = A.dev(Xq), A.dev(Xdb)
     n0 = lib.gll_query_launches()
     _G().knn_query(aq, adb, k)
     n1 = lib.gll_query_launches()
@@ -250,7 +245,7 @@ def test_evaluation_shape_stays_within_its_workspace():
     cen = rng.standard_normal((10, d)).astype(np.float32)
     Xdb = cen[rng.integers(0, 10, size=N)] + 0.3 * rng.standard_normal((N, d)).astype(np.float32)
     Xq = cen[rng.integers(0, 10, size=Q)] + 0.3 * rng.standard_normal((Q, d)).astype(np.float32)
-    aq, adb = _dev(Xq), _dev(Xdb)
+    aq, adb = A.dev(Xq), A.dev(Xdb)
     ws = _L().lib().gll_query_workspace_bytes(Q, N, d, k, 0)
     assert ws < 140 * 2 ** 20 < Q * N * 4
     torch.cuda.synchronize()

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import abi as A
 from tests import query_ref as R
 from tests import rerank_ref as RR
 
@@ -32,9 +33,7 @@ def _G():
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    _L().lib()  # fail loudly when the HIP library is missing
+    A.need_gpu()
     yield
     try:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
@@ -42,14 +41,6 @@ def _need_gpu():
             json.dump(PARITY, fh, indent=1, sort_keys=True)
     except OSError:
         pass
-
-
-def _dev(a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()   # a copy: the cases are read-only
-
-
-def _bits(t):
-    return None if t is None else t.detach().cpu().numpy().tobytes()
 
 
 def _shifted(a):
@@ -90,7 +81,7 @@ def _check_d2(d2, d2_ref, d):
 def test_pool_mode_against_float64(name):
     Xq, Xdb, cand, k, idx_ref, d2_ref, st_ref, det = RR.pool(name)
     d = Xdb.shape[1]
-    xq, xdb, cd = _dev(Xq), _dev(Xdb), _dev(cand)
+    xq, xdb, cd = A.dev(Xq), A.dev(Xdb), A.dev(cand)
     assert xq.data_ptr() % 16 == 0 and xdb.data_ptr() % 16 == 0
     idx, d2, st = _raw(xq, xdb, cd, k)
     print(name, "status", st, "reference", st_ref)
@@ -121,16 +112,16 @@ def test_list_mode_against_float64_and_the_pool_bits(name):
     d, N = Xdb.shape[1], Xdb.shape[0]
     lst = np.ascontiguousarray(cand[:, :k])
     idx_ref, d2_ref, st_ref = RR.rerank_ref(Xq, Xdb, lst, k, keep_order=True)
-    xq, xdb = _dev(Xq), _dev(Xdb)
-    idx, d2, st = _raw(xq, xdb, _dev(lst), k, _L().RR_KEEP_ORDER)
+    xq, xdb = A.dev(Xq), A.dev(Xdb)
+    idx, d2, st = _raw(xq, xdb, A.dev(lst), k, _L().RR_KEEP_ORDER)
     assert (idx == lst).all()                     # as they are: repeats and indices out of range
     _check_d2(d2, d2_ref, d)
     assert np.isposinf(d2[(lst < 0) | (lst >= N)]).all()
     assert st == st_ref
-    again = _raw(_shifted(Xq), _shifted(Xdb), _dev(lst), k, _L().RR_KEEP_ORDER)
+    again = _raw(_shifted(Xq), _shifted(Xdb), A.dev(lst), k, _L().RR_KEEP_ORDER)
     assert again[0].tobytes() == idx.tobytes() and again[1].tobytes() == d2.tobytes()
     # a pair (q, j) has one distance, whichever mode and slot computed it
-    pi, pd, _ = _raw(xq, xdb, _dev(cand), min(cand.shape[1], 256))
+    pi, pd, _ = _raw(xq, xdb, A.dev(cand), min(cand.shape[1], 256))
     for q in range(len(Xq)):
         by_j = {int(j): f.tobytes() for j, f in zip(pi[q], pd[q]) if j >= 0}
         for j, f in zip(lst[q], d2[q]):
@@ -143,7 +134,7 @@ def test_k_may_exceed_the_database():
     for N, c, k in ((1, 512, 256), (2, 9, 9), (2, 256, 256)):
         Xq, Xdb, cand = RR._pool(100 + N, 5, N, 4, c, lo=-1)
         idx_ref, d2_ref, st_ref = RR.rerank_ref(Xq, Xdb, cand, k)
-        idx, d2, st = _raw(_dev(Xq), _dev(Xdb), _dev(cand), k)
+        idx, d2, st = _raw(A.dev(Xq), A.dev(Xdb), A.dev(cand), k)
         assert (idx == idx_ref).all() and st == st_ref and st[3] == 5
         _check_d2(d2, d2_ref, 4)
 
@@ -155,28 +146,28 @@ def test_k_may_exceed_the_database():
                                   "sphere_overflow", "lattice"])
 def test_lists_and_shuffled_pools_return_the_search_bits(name):
     Xq, Xdb, k, cand = RR.shuffled_pool(name)
-    xq, xdb = _dev(Xq), _dev(Xdb)
+    xq, xdb = A.dev(Xq), A.dev(Xdb)
     idx, d2 = _G().knn_query(xq, xdb, k)
     li, ld, ls = _G().knn_query(xq, xdb, k, candidates=idx, keep_order=True, return_status=True)
     assert li.dtype == torch.int64 and ld.dtype == torch.float32
-    assert _bits(li) == _bits(idx) and _bits(ld) == _bits(d2) and ls.cpu().tolist() == [0, 0, 0, 0]
-    for pool in (_dev(cand), torch.from_numpy(np.array(cand)).int()):    # int64 on the device, int32 on the host
+    assert A.raw_bytes(li) == A.raw_bytes(idx) and A.raw_bytes(ld) == A.raw_bytes(d2) and ls.cpu().tolist() == [0, 0, 0, 0]
+    for pool in (A.dev(cand), torch.from_numpy(np.array(cand)).int()):    # int64 on the device, int32 on the host
         pi, pd, ps = _G().knn_query(xq, xdb, k, candidates=pool, return_status=True)
-        assert _bits(pi) == _bits(idx) and _bits(pd) == _bits(d2) and ps.cpu().tolist() == [0, 0, 0, 0]
+        assert A.raw_bytes(pi) == A.raw_bytes(idx) and A.raw_bytes(pd) == A.raw_bytes(d2) and ps.cpu().tolist() == [0, 0, 0, 0]
 
 
 def _ext_inputs(name, grad):
     Xq, Xdb, P, k, epsilon, eps_db, *_ = R.ext_case(name)
-    xq, xdb, p = (_dev(a).requires_grad_(grad) for a in (Xq, Xdb, P))
+    xq, xdb, p = (A.dev(a).requires_grad_(grad) for a in (Xq, Xdb, P))
     eps = epsilon
     if epsilon != "auto" and grad:
         eps = torch.tensor(float(epsilon), dtype=torch.float64, device="cuda", requires_grad=True)
-    return xq, xdb, p, eps, None if eps_db is None else _dev(eps_db), k
+    return xq, xdb, p, eps, None if eps_db is None else A.dev(eps_db), k
 
 
 @pytest.mark.parametrize("name", list(R.EXT_CASES))
 def test_extend_on_the_search_lists_is_extend(name):
-    gU = _dev(np.random.default_rng(7).standard_normal(R.ext_case(name)[6].shape))
+    gU = A.dev(np.random.default_rng(7).standard_normal(R.ext_case(name)[6].shape))
 
     def run(neighbors):
         xq, xdb, p, eps, e, k = _ext_inputs(name, True)
@@ -186,12 +177,12 @@ def test_extend_on_the_search_lists_is_extend(name):
         (Uq * gU).sum().backward()
         grads = [xq.grad, xdb.grad, p.grad, eps.grad if torch.is_tensor(eps) else None]
         assert st.cpu().tolist()[1:] == [0, 0, 0]          # (word 0 counts the search's rescans)
-        return [_bits(t) for t in (Uq, lab, *grads)]
+        return [A.raw_bytes(t) for t in (Uq, lab, *grads)]
 
     Xq, Xdb, P, k, *_ = R.ext_case(name)
     kn = k - 1
-    idx = _G().knn_query(_dev(Xq), _dev(Xdb), kn)[0]
-    wide = _G().knn_query(_dev(Xq), _dev(Xdb), 2 * kn)[0]
+    idx = _G().knn_query(A.dev(Xq), A.dev(Xdb), kn)[0]
+    wide = _G().knn_query(A.dev(Xq), A.dev(Xdb), 2 * kn)[0]
     perm = torch.from_numpy(np.random.default_rng(8).permutation(2 * kn)).cuda()
     ref = run(None)
     assert run(idx) == ref                        # list mode: the caller's order is the search's
@@ -200,7 +191,7 @@ def test_extend_on_the_search_lists_is_extend(name):
     xq, xdb, p, eps, e, k = _ext_inputs(name, False)
     a = _G().extend(xq, xdb, p, k=k, epsilon=eps, eps_db=e)
     b = _G().extend(xq, xdb, p, k=k, epsilon=eps, eps_db=e, neighbors=idx.cpu())
-    assert b[0].grad_fn is None and _bits(a[0]) == _bits(b[0]) == ref[0] and torch.equal(a[1], b[1])
+    assert b[0].grad_fn is None and A.raw_bytes(a[0]) == A.raw_bytes(b[0]) == ref[0] and torch.equal(a[1], b[1])
 
 
 # ------------------------------------------------------------------------------------------
@@ -241,16 +232,16 @@ def _torch_grads(name, dtype, device):
 def test_moved_queries_on_frozen_lists(name):
     Xq, Xdb, P, k, epsilon, eps_db, *_ = R.ext_case(name)
     Xm, idx, Uq_ref, lab_ref, bound, gU = _moved(name)
-    xq, xdb, p = (_dev(a).requires_grad_(True) for a in (Xm, Xdb, P))
+    xq, xdb, p = (A.dev(a).requires_grad_(True) for a in (Xm, Xdb, P))
     eps = epsilon
     if epsilon != "auto":
         eps = torch.tensor(float(epsilon), dtype=torch.float64, device="cuda", requires_grad=True)
     Uq, lab, st = _G().extend(xq, xdb, p, k=k, epsilon=eps, return_status=True,
-                              eps_db=None if eps_db is None else _dev(eps_db), neighbors=_dev(idx))
+                              eps_db=None if eps_db is None else A.dev(eps_db), neighbors=A.dev(idx))
     err = np.abs(Uq.detach().cpu().numpy() - Uq_ref).max()
     print(name, "max |Uq - ref|", err, "bound", bound)
     assert err <= bound and (lab.cpu().numpy() == lab_ref).all() and st.cpu().tolist() == [0, 0, 0, 0]
-    (Uq * _dev(gU)).sum().backward()
+    (Uq * A.dev(gU)).sum().backward()
     ours = [xq.grad, xdb.grad, p.grad, None if epsilon == "auto" else eps.grad.reshape(1)]
     ref = _torch_grads(name, torch.float64, "cpu")
     f32 = _torch_grads(name, torch.float32, "cuda")
@@ -267,13 +258,13 @@ def test_moved_queries_on_frozen_lists(name):
         assert mine <= 8 * theirs
     # a pool re-ranked at the moved queries is the search at the moved queries while it holds them
     kn = k - 1
-    pool = _G().knn_query(_dev(Xq), xdb.detach(), min(4 * kn, 256))[0]
-    si, sd = _G().knn_query(_dev(Xm), xdb.detach(), kn)
-    pi, pd = _G().knn_query(_dev(Xm), xdb.detach(), kn, candidates=pool)
+    pool = _G().knn_query(A.dev(Xq), xdb.detach(), min(4 * kn, 256))[0]
+    si, sd = _G().knn_query(A.dev(Xm), xdb.detach(), kn)
+    pi, pd = _G().knn_query(A.dev(Xm), xdb.detach(), kn, candidates=pool)
     held = (np.sort(R.knn_ref(Xm, Xdb, kn)[0], axis=1)[:, :, None] == pool.cpu().numpy()[:, None, :]).any(2).all(1)
     assert held.mean() > 0.5
     h = torch.from_numpy(held).cuda()
-    assert _bits(pi[h]) == _bits(si[h]) and _bits(pd[h]) == _bits(sd[h])
+    assert A.raw_bytes(pi[h]) == A.raw_bytes(si[h]) and A.raw_bytes(pd[h]) == A.raw_bytes(sd[h])
 
 
 # ------------------------------------------------------------------------------------------
@@ -282,7 +273,7 @@ def test_moved_queries_on_frozen_lists(name):
 @pytest.mark.parametrize("name", ["hard", "nonfinite", "d36_c64", "c512_k256"])
 def test_row_of_a_call_equals_the_call_on_that_row(name):
     Xq, Xdb, cand, k, *_ = RR.pool(name)
-    xq, xdb, cd = _dev(Xq), _dev(Xdb), _dev(cand)
+    xq, xdb, cd = A.dev(Xq), A.dev(Xdb), A.dev(cand)
     idx, d2, _ = _raw(xq, xdb, cd, k)
     for q in range(len(Xq)):
         i1, f1, _ = _raw(xq[q:q + 1].clone(), xdb, cd[q:q + 1].clone(), k)
@@ -294,7 +285,7 @@ def test_launches_per_call():
     launches what it did (three a panel + the extension)."""
     lib = _L().lib()
     Xq, Xdb, P, k, epsilon, eps_db, *_ = R.ext_case("auto")
-    xq, xdb, p, e = _dev(Xq), _dev(Xdb), _dev(P), _dev(eps_db)
+    xq, xdb, p, e = A.dev(Xq), A.dev(Xdb), A.dev(P), A.dev(eps_db)
     idx = _G().knn_query(xq, xdb, k - 1)[0]
     wide = _G().knn_query(xq, xdb, 3 * (k - 1))[0]
     n = [lib.gll_query_launches()]
@@ -324,7 +315,7 @@ def test_launches_per_call():
 def test_short_pool_rows_and_bad_list_entries_are_nan_and_counted():
     L = _L()
     Xq, Xdb, P, k, epsilon, eps_db, *_ = R.ext_case("fixed")
-    xq, xdb, p = _dev(Xq), _dev(Xdb), _dev(P)
+    xq, xdb, p = A.dev(Xq), A.dev(Xdb), A.dev(P)
     kn, N = k - 1, len(Xdb)
     idx = _G().knn_query(xq, xdb, kn)[0]
     clean = _G().extend(xq, xdb, p, k=k, epsilon=epsilon)[0]
@@ -332,13 +323,13 @@ def test_short_pool_rows_and_bad_list_entries_are_nan_and_counted():
     pool[3, :kn + 2] = idx[3, 0]                  # row 3: kn - 1 valid entries
     Uq, lab, st = _G().extend(xq, xdb, p, k=k, epsilon=epsilon, neighbors=pool, return_status=True)
     keep = [q for q in range(len(Xq)) if q != 3]
-    assert torch.isnan(Uq[3]).all() and _bits(Uq[keep]) == _bits(clean[keep])
+    assert torch.isnan(Uq[3]).all() and A.raw_bytes(Uq[keep]) == A.raw_bytes(clean[keep])
     assert st.cpu().tolist() == [0, 0, 1, 1]      # the short row, and its NaN weight sum
     bad = idx.clone()
     bad[5, 2], bad[6, 0] = N, -1                  # list mode keeps them and does not follow them
     Uq, lab, st = _G().extend(xq, xdb, p, k=k, epsilon=epsilon, neighbors=bad, return_status=True)
     keep = [q for q in range(len(Xq)) if q not in (5, 6)]
-    assert torch.isnan(Uq[[5, 6]]).all() and _bits(Uq[keep]) == _bits(clean[keep])
+    assert torch.isnan(Uq[[5, 6]]).all() and A.raw_bytes(Uq[keep]) == A.raw_bytes(clean[keep])
     assert st.cpu().tolist() == [0, 2, 2, 0]
     i0, f0 = _G().knn_query(xq[:0], xdb, 3, candidates=idx[:0])
     assert i0.shape == (0, 3) and i0.dtype == torch.int64 and f0.shape == (0, 3)
@@ -357,21 +348,21 @@ def test_laplace_predict_on_lists_and_pools(epsilon):
     X = (cen[lab] + 0.5 * rng.standard_normal((n, d))).astype(np.float32)
     Xq = (cen[np.arange(40) % C] + 0.5 * rng.standard_normal((40, d))).astype(np.float32)
     fit = utils.laplace_fit(X, lab[:base], knn_num=kk, epsilon=epsilon)
-    xq = _dev(Xq)
+    xq = A.dev(Xq)
     Uq, labels = utils.laplace_predict(fit, xq, knn_num=kk)
     idx = _G().knn_query(xq, fit.X, kk - 1)[0]
     pool = _G().knn_query(xq, fit.X, 4 * (kk - 1))[0]
     for nb in (idx, pool):
         a = xq.clone().requires_grad_(True)
         Un, ln = utils.laplace_predict(fit, a, knn_num=kk, neighbors=nb)
-        assert _bits(Un) == _bits(Uq) and torch.equal(ln, labels) and Un.grad_fn is not None
+        assert A.raw_bytes(Un) == A.raw_bytes(Uq) and torch.equal(ln, labels) and Un.grad_fn is not None
         Un.sum().backward()
         assert torch.isfinite(a.grad).all()
     # the attack loop: the pool searched once, re-ranked at every step's features
     Xs = (Xq + 0.05 * rng.standard_normal(Xq.shape)).astype(np.float32)
     near = R.knn_ref(Xs, X, kk - 1)[0]
     assert (near[:, :, None] == pool.cpu().numpy()[:, None, :]).any(2).all()   # the pool holds them
-    step = _dev(Xs)
+    step = A.dev(Xs)
     Us, ls = utils.laplace_predict(fit, step, knn_num=kk)
     Up, lp = utils.laplace_predict(fit, step, knn_num=kk, neighbors=pool)
-    assert _bits(Up) == _bits(Us) and torch.equal(lp, ls)
+    assert A.raw_bytes(Up) == A.raw_bytes(Us) and torch.equal(lp, ls)

@@ -35,13 +35,15 @@ directed knn_d2 (hub and near-tie cases, where the select re-ranks a row in floa
 maximum was exercised on the MI355X as well as in the CPU reference.  No tolerance is tuned to
 these figures: KAPPA_E is an assumption stated in rows_ref.py, the rest is counted from the code.
 """
-import ctypes as ct
 import time
 
 import numpy as np
 import pytest
 import torch
 
+from graphlearninglayer_amd import GLL
+from graphlearninglayer_amd import _lib as L
+from tests import abi as A
 from tests import rows_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -50,21 +52,9 @@ _stats = {}        # quantity -> [elements, worst err/bound]
 _record = {"mutual": 0, "mutual_diff": 0, "graphs": 0, "t0": None}
 
 
-def _lib():
-    from graphlearninglayer_amd import _lib
-    return _lib
-
-
-def _gll():
-    from graphlearninglayer_amd import GLL
-    return GLL
-
-
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    _lib().lib()  # fail loudly when the HIP library is missing
+    A.need_gpu()
     _record["t0"] = time.perf_counter()
     yield
     print(f"\nrows stage: {_record['graphs']} graphs, {time.perf_counter() - _record['t0']:.1f} s")
@@ -75,75 +65,38 @@ def _need_gpu():
           "two different directed knn_d2")
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 class Session:
-    """One case on the device: the features and labels of its B graphs, B workspace blocks of
-    0xFF bytes, one forward with GLL_K_FINALIZE bracketed."""
+    """One case on the device (tests/abi.py Run): the features and labels of its B graphs, B
+    workspace blocks of 0xFF bytes, one forward with GLL_K_FINALIZE bracketed."""
 
     def __init__(self, case, B=None, graphs=None):
-        L = _lib()
         self.case = c = case
         self.B = B = c.B if B is None else B
         self.graphs = list(range(B)) if graphs is None else graphs     # feature seeds
         self.lay = c.layout()
-        self.Xh = np.stack([R.features(c, g) for g in self.graphs])
+        Xh = np.stack([R.features(c, g) for g in self.graphs])
         self.Yh = [R.labels(c, g) for g in self.graphs]
-        self.X = torch.from_numpy(self.Xh).cuda()
-        self.Y = torch.from_numpy(np.stack(self.Yh)).cuda() if c.base else None
-        p = self.problem()
-        self.wb = L.lib().gll_workspace_bytes(ct.byref(p))
-        assert self.wb > 0
-        self.ws = torch.full((B * self.wb,), 0xFF, dtype=torch.uint8, device="cuda")
-        self.U = torch.full((B, c.m, c.C), float("nan"), dtype=torch.float64, device="cuda")
-        ydt = {"f32": L.GLL_DT_F32, "f64": L.GLL_DT_F64, "i64": L.GLL_DT_I64}[c.y_dtype]
-        yp = self.Y.data_ptr() if c.base else None
-        L.prof_read(L.K_FINALIZE)
-        L.prof_enable(L.K_FINALIZE, 1)
-        try:
-            L.set_knob(L.KNOB_ROW_PRE, c.knob_pre)
+        one = B == 1
+        Y = (self.Yh[0] if one else np.stack(self.Yh)) if c.base else None
+        self.run = A.Run(Xh[0] if one else Xh, Y, c.K, R.TAU, c.eps, c.flags, C=c.C, ws_fill=0xFF,
+                         y_dtype=c.y_dtype)
+        with A.knobs({L.KNOB_ROW_PRE: c.knob_pre}), A.launches(L.K_FINALIZE) as ran:
             if c.graph_api:
                 assert B == 1 and c.base == 0
-                rc = L.lib().gll_graph(ct.byref(p), self.X.data_ptr(), self.ws.data_ptr(), _stream())
-            elif B == 1:
-                rc = L.lib().gll_forward(ct.byref(p), self.X.data_ptr(), yp, ydt, self.ws.data_ptr(),
-                                         self.U.data_ptr(), _stream())
+                self.run.graph()
             else:
-                rc = L.lib().gll_forward_batched(ct.byref(p), B, self.X.data_ptr(), yp, ydt,
-                                                 self.ws.data_ptr(), self.U.data_ptr(), _stream())
-            L.check(rc, "gll_forward")
-            torch.cuda.synchronize()
-            self.launches = L.prof_read(L.K_FINALIZE)[1]
-        finally:
-            L.set_knob(L.KNOB_ROW_PRE, 0)
-            L.prof_enable(L.K_FINALIZE, 0)
-        self.host = self.ws.cpu().numpy()
-
-    def problem(self):
-        c = self.case
-        return _gll().make_problem(c.n, R.D, c.base, c.C, c.K, R.TAU, c.eps, flags=c.flags)
-
-    def _arr(self, g, ptr, count, dtype):
-        off = ptr - self.ws.data_ptr()
-        assert g * self.wb <= off and off + count * np.dtype(dtype).itemsize <= (g + 1) * self.wb
-        return self.host[off: off + count * np.dtype(dtype).itemsize].view(dtype)
+                self.run.forward()
+        self.launches = ran[0]
+        self.host = self.run.host_copy()
 
     def graph(self, q):
         """(Stage on the GPU's own lists, Out) of graph number q of the batch."""
-        L = _lib()
-        c, lay = self.case, self.lay
-        v, sv = L.View(), L.SolveView()
-        p = self.problem()
-        ws = self.ws.data_ptr() + q * self.wb
-        L.check(L.lib().gll_workspace_view(ct.byref(p), ws, ct.byref(v)), "gll_workspace_view")
-        L.check(L.lib().gll_workspace_solve_view(ct.byref(p), ws, ct.byref(sv)),
-                "gll_workspace_solve_view")
+        c, lay, run = self.case, self.lay, self.run
+        v, sv = run.view(q), run.solve_view(q)
         assert (sv.SE, sv.VRM, sv.Wcap, sv.RCAP) == (lay.SE, lay.VRM, lay.Wcap, lay.RCAP)
         i32, f32 = np.int32, np.float32
         n, m, C, K = c.n, c.m, c.C, lay.K
-        a = lambda ptr, count, dt: self._arr(q, ptr, count, dt)
+        a = lambda ptr, count, dt: run.array(ptr, count, dt, q, snapshot=self.host)
         idx = a(v.knn_idx, n * K, i32).reshape(n, K)
         d2 = a(v.knn_d2, n * K, f32).reshape(n, K)
         eps = a(v.eps, n, f32)
@@ -270,7 +223,7 @@ def test_device_graph_compacts_the_padded_rows_of_the_view():
                   graph_api=True, seed=hub.seed)
     (st, out), = _hold(Session(case))
     assert "bump+lds+ovf" in R.regimes(st, case)
-    g = _gll().device_graph(torch.from_numpy(R.features(case)), case.K, 1.0)
+    g = GLL.device_graph(torch.from_numpy(R.features(case)), case.K, 1.0)
     rl, col, w, d2 = _compact(st, out)[:4]
     assert np.array_equal(g["row_ptr"].cpu().numpy(), np.r_[0, np.cumsum(rl)])
     assert np.array_equal(g["col"].cpu().numpy(), col)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import abi as A
 from tests import supcon_ref as S
 
 pytestmark = pytest.mark.gpu
@@ -33,9 +34,7 @@ def _M():
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    _L().lib()  # fail loudly when the HIP library is missing
+    A.need_gpu()
     yield
     try:
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)

@@ -10,13 +10,12 @@ import torch
 
 from graphlearninglayer_amd.synth import CONFIGS, one_hot, seeded_gbar, synth
 from oracle import gll_oracle as O
+from tests import abi as A
 from tests import unit_ref as R
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4                      # the project's parity bar (tests/test_gpu_parity.py)
 DT = {"float32": torch.float32, "float16": torch.float16, "bfloat16": torch.bfloat16}
-BITS = {torch.float32: torch.int32, torch.float16: torch.int16, torch.bfloat16: torch.int16,
-        torch.float64: torch.int64}
 SENT = -7.25                    # guard value, exact in every dtype
 
 
@@ -32,23 +31,11 @@ def _L():
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    _L().lib()  # fail loudly when the HIP library is missing
+    A.need_gpu()
 
 
 def _calls():
     return _L().lib().gll_features_calls()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and \
-        torch.equal(a.contiguous().view(BITS.get(a.dtype, a.dtype)),
-                    b.contiguous().view(BITS.get(b.dtype, b.dtype)))
 
 
 def _guarded(rows, d, dtype):
@@ -71,7 +58,7 @@ def _forward_raw(Z, normalize, with_rnorm=True):
     code = {torch.float32: L.XT_F32, torch.float16: L.XT_F16, torch.bfloat16: L.XT_BF16}[Z.dtype]
     rc = L.lib().gll_features_forward(rows, d, Z.data_ptr(), code,
                                       L.UF_NORMALIZE if normalize else 0, X.data_ptr(),
-                                      rn.data_ptr() if with_rnorm else None, _stream())
+                                      rn.data_ptr() if with_rnorm else None, A.stream())
     assert rc == 0
     torch.cuda.synchronize()
     return X, rn, Xbig, rbig
@@ -86,7 +73,7 @@ def _backward_raw(gX, X, rn, dtype, normalize):
                                        X.data_ptr() if normalize else None,
                                        rn.data_ptr() if normalize else None,
                                        L.UF_NORMALIZE if normalize else 0, gZ.data_ptr(), code,
-                                       _stream())
+                                       A.stream())
     assert rc == 0
     torch.cuda.synchronize()
     return gZ, gbig
@@ -152,7 +139,7 @@ def test_forward_pass_through_is_the_exact_widening(rows, d, name):
         want = Z.float()
         nan = torch.isnan(want)
         assert torch.equal(torch.isnan(X), nan)
-        assert _same_bits(torch.where(nan, 0.0, X), torch.where(nan, 0.0, want))
+        assert A.same_bits(torch.where(nan, 0.0, X), torch.where(nan, 0.0, want))
         assert bool((rbig == SENT).all())        # rnorm is not touched
         assert _guards_intact(Xbig)
 
@@ -184,7 +171,7 @@ def test_backward_stage_within_the_derived_bound(rows, d, name):
     # a clamped row is one fp32 multiplication r g, rounded once (fp16: 1e12 g overflows to inf)
     if cl.any():
         c = torch.from_numpy(cl).cuda()
-        assert _same_bits(gZ[c], (rn[c, None] * g[c]).to(dt))
+        assert A.same_bits(gZ[c], (rn[c, None] * g[c]).to(dt))
 
 
 @pytest.mark.parametrize("name", list(DT))
@@ -195,7 +182,7 @@ def test_backward_pass_through_is_the_cast(rows, d, name):
     g = (rng.standard_normal((rows, d)) * 10.0 ** rng.uniform(-9, 6, size=(rows, d)))
     g = torch.from_numpy(g.astype(np.float32)).cuda()    # past fp16's range both ways
     gZ, gbig = _backward_raw(g, None, None, dt, False)
-    assert _same_bits(gZ, g.to(dt)) and _guards_intact(gbig)
+    assert A.same_bits(gZ, g.to(dt)) and _guards_intact(gbig)
 
 
 # ------------------------------------------------------------------------------------------
@@ -212,7 +199,7 @@ def test_rows_do_not_depend_on_their_place(rows, d, name):
     gZ = G.unit_features_backward(g, X, rn, dt)
     Xp, rnp = G.unit_features(Z[perm].contiguous())
     gZp = G.unit_features_backward(g[perm].contiguous(), Xp, rnp, dt)
-    assert _same_bits(Xp, X[perm]) and _same_bits(rnp, rn[perm]) and _same_bits(gZp, gZ[perm])
+    assert A.same_bits(Xp, X[perm]) and A.same_bits(rnp, rn[perm]) and A.same_bits(gZp, gZ[perm])
 
 
 @pytest.mark.parametrize("name", list(DT))
@@ -228,8 +215,8 @@ def test_a_batch_is_its_separate_calls(B, n, d, name):
     assert X.shape == (B, n, d) and rn.shape == (B, n) and gZ.shape == (B, n, d)
     for b in range(B):
         Xb, rb = G.unit_features(Z[b].clone())
-        assert _same_bits(Xb, X[b]) and _same_bits(rb, rn[b])
-        assert _same_bits(G.unit_features_backward(g[b].clone(), Xb, rb, dt), gZ[b])
+        assert A.same_bits(Xb, X[b]) and A.same_bits(rb, rn[b])
+        assert A.same_bits(G.unit_features_backward(g[b].clone(), Xb, rb, dt), gZ[b])
 
 
 def test_more_rows_than_one_launch_holds():
@@ -247,7 +234,7 @@ def test_more_rows_than_one_launch_holds():
     g = torch.randn(rows, 1, device="cuda", generator=torch.Generator("cuda").manual_seed(2))
     gZ = G.unit_features_backward(g, None, None, torch.bfloat16, normalize=False)
     assert _calls() - c0 == 4
-    assert _same_bits(gZ, g.to(torch.bfloat16))
+    assert A.same_bits(gZ, g.to(torch.bfloat16))
 
 
 # ------------------------------------------------------------------------------------------
@@ -298,10 +285,10 @@ def test_layer_with_normalize_is_bitwise_its_stages(shape, eps, B, name):
     XB, (YB, tauB) = Xh.clone().requires_grad_(True), _leaves(Y)
     UB = F.apply(XB, YB, tauB, eps, k)
     UB.backward(gbar)
-    assert _same_bits(UA.detach(), UB.detach())
+    assert A.same_bits(UA.detach(), UB.detach())
     assert zA.grad.dtype == z.dtype
-    assert _same_bits(zA.grad, G.unit_features_backward(XB.grad, Xh, rn, z.dtype))
-    assert _same_bits(YA.grad, YB.grad) and _same_bits(tauA.grad, tauB.grad)
+    assert A.same_bits(zA.grad, G.unit_features_backward(XB.grad, Xh, rn, z.dtype))
+    assert A.same_bits(YA.grad, YB.grad) and A.same_bits(tauA.grad, tauB.grad)
     # ce_loss (normalize given positionally)
     zC, (YC, tauC) = z.clone().requires_grad_(True), _leaves(Y)
     outC = F.ce_loss(zC, YC, t, tauC, eps, k, True)
@@ -310,10 +297,10 @@ def test_layer_with_normalize_is_bitwise_its_stages(shape, eps, B, name):
     outD = F.ce_loss(XD, YD, t, tauD, eps, k)
     outD[0].sum().backward()
     for a, b in zip(outC, outD):
-        assert _same_bits(a.detach(), b.detach())
-    assert _same_bits(outC[1], UA.detach())
-    assert _same_bits(zC.grad, G.unit_features_backward(XD.grad, Xh, rn, z.dtype))
-    assert _same_bits(YC.grad, YD.grad) and _same_bits(tauC.grad, tauD.grad)
+        assert A.same_bits(a.detach(), b.detach())
+    assert A.same_bits(outC[1], UA.detach())
+    assert A.same_bits(zC.grad, G.unit_features_backward(XD.grad, Xh, rn, z.dtype))
+    assert A.same_bits(YC.grad, YD.grad) and A.same_bits(tauC.grad, tauD.grad)
 
 
 # ------------------------------------------------------------------------------------------
@@ -336,7 +323,7 @@ def test_fp32_without_normalize_takes_the_old_route(B):
     U1, g1, f1, b1 = _fwd_bwd(z, Y, gbar, k, False)
     U2, g2, f2, b2 = _fwd_bwd(z, Y, gbar, k, False)
     assert (f1, b1, f2, b2) == (0, 0, 0, 0)
-    assert _same_bits(U1, U2) and _same_bits(g1, g2)
+    assert A.same_bits(U1, U2) and A.same_bits(g1, g2)
     F = _G().LaplaceLearningSparseHard
     zl = z.clone().requires_grad_(True)
     c0 = _calls()
@@ -352,7 +339,7 @@ def test_half_features_without_normalize_convert_once_each_way(B, name):
     assert (f, b) == (1, 1)
     U32, g32, f32, b32 = _fwd_bwd(z.float(), Y, gbar, k, False)
     assert (f32, b32) == (0, 0)
-    assert _same_bits(U, U32) and g.dtype == z.dtype and _same_bits(g, g32.to(z.dtype))
+    assert A.same_bits(U, U32) and g.dtype == z.dtype and A.same_bits(g, g32.to(z.dtype))
 
 
 @pytest.mark.parametrize("name", list(DT))
@@ -423,7 +410,7 @@ def test_cpu_bf16_input_comes_back_to_the_cpu():
     assert Uc.device.type == "cpu" and Uc.dtype == torch.float64
     Uc.backward(gbar.cpu())
     assert zc.grad.device.type == "cpu" and zc.grad.dtype == torch.bfloat16
-    assert _same_bits(Uc, Ud.detach().cpu()) and _same_bits(zc.grad, zd.grad.cpu())
+    assert A.same_bits(Uc, Ud.detach().cpu()) and A.same_bits(zc.grad, zd.grad.cpu())
 
 
 @pytest.mark.parametrize("name", ["float32", "float16"])
@@ -436,7 +423,7 @@ def test_noncontiguous_input(name):
     Ua, Ub = F.apply(za, Y, 0.05, 1.0, k, True), F.apply(zb, Y, 0.05, 1.0, k, True)
     Ua.backward(gbar)
     Ub.backward(gbar)
-    assert _same_bits(Ua.detach(), Ub.detach()) and _same_bits(za.grad, zb.grad)
+    assert A.same_bits(Ua.detach(), Ub.detach()) and A.same_bits(za.grad, zb.grad)
 
 
 def test_float64_input_gets_a_float64_gradient():
@@ -477,4 +464,4 @@ def test_repeated_backward(name):
     g1 = zr.grad.clone()
     zr.grad = None
     U.backward(gbar)
-    assert _same_bits(g1, zr.grad) and _same_bits(g1, zl.grad)
+    assert A.same_bits(g1, zr.grad) and A.same_bits(g1, zl.grad)
